@@ -8,11 +8,16 @@ step runs athd.dist.separate_segments, so the point-to-point RCCL gather of all 
 (xGMI) is inside the timed region, overlapped with the next step's compute.  Timing = barrier + sync around K steps,
 max over ranks.
 
-Beside the headline (all outside the timed region, rank 0): the roofline of the dominant kernel (HIP events) and of
-each forward section, the whole-step MFMA fraction, the bf16 output's SDR against the fp32 oracle, an f32-mode
-(parity mode) throughput line, and the CPU baseline (the oracle on the host's cores).
+A plain run sets up, warms up (W steps of the timed path), times the K steps and prints the headline line.
+`--dump-outputs DIR` also writes what the last timed step computed (DIR/<name>.npy, float32; see dump_outputs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|f32] [--no-cpu-baseline]
+With `--full`, beside the headline (all outside the timed region, rank 0): the roofline of the dominant kernel (HIP
+events) and of each forward section, the whole-step MFMA fraction, the bf16 output's SDR against the fp32 oracle, an
+f32-mode (parity mode) throughput line, and the CPU baseline (the oracle on the host's cores).  `--dump-kernels`,
+`--kernel` and `--segments` belong to these measurements and need `--full`; `--no-cpu-baseline` / `--no-extras` trim it.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|f32] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extras] [--dump-kernels F.json] [--segments N]]
 """
 import argparse
 import json
@@ -37,6 +42,8 @@ F32_PEAK_TFLOPS = 157.3
 HBM_PEAK_GBS = 8000.0
 MFMA_KERNELS = ("gemm", "attn", "fenc_row")   # kernel-name prefixes priced against the MFMA peak; the rest HBM
 ROOF_STEPS = 2
+DUMP_SAMPLE = 1 << 21         # --dump-outputs: elements in the seeded sample of the whole output (8 MB as float32)
+DUMP_SEED = 2718
 PMC_FILE = os.environ.get("ATHD_PMC_TRAFFIC", os.path.join(REPO, "profiles", "pmc_traffic.json"))
 
 
@@ -80,6 +87,16 @@ def cpu_info():
     except OSError:
         pass
     return usable, host, model
+
+
+def bench_batch(B, seed0):
+    """athd.synth.synthetic_batch(B, SEG, seed0) with the segments generated side by side on the usable cores (each
+    segment has its own seeded generator and numpy's array loops release the GIL): the same values bit for bit in a
+    fraction of the set-up time (64 segments take ~30 s on one core)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from athd.synth import synthetic_mixture
+    with ThreadPoolExecutor(max_workers=min(16, cpu_info()[0])) as ex:
+        return np.stack(list(ex.map(lambda i: synthetic_mixture(SEG, seed0 + i), range(B))))
 
 
 def cpu_baseline(sd, table):
@@ -288,15 +305,36 @@ def dataset_pass(model, wav, n, batch, world, rank, dev):
                        "batch": batch, "prompts": 4, "parallelism": f"segment-sharded dp{world}"}}
 
 
-def main():
+def dump_outputs(dirname, out):
+    """--dump-outputs: the (N, 4, 2, T) float32 result of the last timed step, i.e. what a caller of the timed path
+    receives, as float32 .npy files of at most 64 MB in all: `stems_rows.npy` = the first, middle and last segment
+    whole (all 4 stems), `stems_sample.npy` = a fixed seeded sample of DUMP_SAMPLE elements of the flattened result
+    (in ascending index order, spread over every segment and stem).  The inputs are seeded, so two builds run with the
+    same arguments write comparable files."""
+    os.makedirs(dirname, exist_ok=True)
+    n = out.shape[0]
+    rows = sorted({0, n // 2, n - 1})
+    np.save(os.path.join(dirname, "stems_rows.npy"), out[rows].cpu().numpy())
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, out.numel(), size=min(DUMP_SAMPLE, out.numel())))
+    sample = out.reshape(-1)[torch.as_tensor(idx, device=out.device)]
+    np.save(os.path.join(dirname, "stems_sample.npy"), sample.cpu().numpy())
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the SDR, f32 and section measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline (per call site and section), the SDR against "
+                         "the oracle, the f32 line and the CPU baseline; the last warm-up step becomes an evented eager "
+                         "forward")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's result to DIR/<name>.npy (float32, see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the SDR, f32 and section measurements")
     ap.add_argument("--decode-items", type=int, default=0,
                     help="(segment, prompt) items per decode chunk (default: the whole batch, B x 4, in one chunk)")
     ap.add_argument("--dump-kernels", default=None, help="write the warmup step's per-kernel profile (JSON)")
@@ -309,7 +347,16 @@ def main():
     ap.add_argument("--segments", type=int, default=0,
                     help="also time one dataset pass of N segments over all ranks (BASELINE configs[3]: ~6k MUSDB18 "
                          "test-set segments) through athd.dist.separate_segments; printed as a second JSON line")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full and (args.dump_kernels or args.kernel or args.segments > 0):
+        ap.error("--dump-kernels, --kernel and --segments are measurements of --full")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -322,7 +369,6 @@ def main():
 
     from athd.dist import PendingSends, separate_segments
     from athd.model import AudioTextHTDemucs
-    from athd.synth import synthetic_batch
     from athd.weights import synthetic_state_dict, synthetic_text_table
 
     sd = synthetic_state_dict(seed=0)
@@ -335,7 +381,7 @@ def main():
     model.load_state_dict(sd)
     model = model.to(dev).eval()
     # B distinct synthetic segments per rank, resident in HBM before timing (weak scaling: each rank owns its block)
-    wav = torch.as_tensor(synthetic_batch(B, SEG, seed0=1000 + B * rank)).to(dev)
+    wav = torch.as_tensor(bench_batch(B, 1000 + B * rank)).to(dev)
     N = B * world
     out = torch.empty((N, len(STEMS), 2, SEG), dtype=torch.float32, device=dev) if rank == 0 else None
     ws_bytes = model._ensure_ctx().workspace_bytes(B, SEG, len(STEMS))
@@ -366,9 +412,9 @@ def main():
             mk = AudioTextHTDemucs(dtype=args.dtype, text_table=tt, decode_items=dec_items)
             mk.load_state_dict(sd)
             mk = mk.to(dev).eval()
-            wk = torch.as_tensor(synthetic_batch(B, SEG, seed0=1000 + B * (world + k))).to(dev)
-            gk, _ = mk.capture_prompts(wk, STEMS)
-            pipes.append((torch.cuda.Stream(dev), gk, mk, wk))
+            wk = torch.as_tensor(bench_batch(B, 1000 + B * (world + k))).to(dev)
+            gk, ok = mk.capture_prompts(wk, STEMS)
+            pipes.append((torch.cuda.Stream(dev), gk, mk, wk, ok))
     nstep = [0]
     ngraph = [0]
 
@@ -395,9 +441,10 @@ def main():
     def fwd_only():
         return model.forward_prompts(wav, STEMS)
 
-    # warmup; the last warmup step times every kernel per call site (HIP events) to find the dominant call site
+    # warmup; with --full the last warmup step times every kernel per call site (HIP events) to find the dominant
+    # call site
     for i in range(args.warmup):
-        if i == args.warmup - 1:
+        if args.full and i == args.warmup - 1:
             model.profile_start("@sites")        # (events around eager launches: the graph's launches are baked)
             fwd_only() if graphs else step()
         else:
@@ -406,7 +453,7 @@ def main():
     torch.cuda.synchronize()
     dominant = args.kernel
     sites = []
-    if args.warmup > 0:
+    if args.full and args.warmup > 0:
         sites = model.profile_stop()
         if args.dump_kernels and rank == 0:
             per_kernel = {}
@@ -450,22 +497,30 @@ def main():
     value = B * world * args.steps / el
     # the timed output, for the parity check below (rank 0's rows of the last step; fwd_only below reuses the
     # model's own workspace and output, not the graph's)
-    timed_rows = out[[0, B - 1]].clone() if rank == 0 else None
+    timed_rows = out[[0, B - 1]].clone() if rank == 0 and args.full else None
+    if args.dump_outputs and rank == 0:
+        # with --pipelines the last step ran on pipeline (steps - 1) % n, each pipeline writing its own output
+        k_last = (args.steps - 1) % (len(pipes) + 1) if pipes else 0
+        dump_outputs(args.dump_outputs, pipes[k_last - 1][4] if k_last > 0 else out)
     peak_mfma = BF16_PEAK_TFLOPS if args.dtype == "bf16" else F32_PEAK_TFLOPS
     flops_step = 2e9 * (ENC_GMAC + 4 * DEC_GMAC) * B
     step_tf = flops_step / (ms * 1e-3) / 1e12
-    roofline = roofline_of(model, fwd_only, dominant, peak_mfma, ms, sites, sections=not args.no_extras)
-    kernel_sym = roofline["kernel"]
-    traffic, traffic_src = pmc_traffic(kernel_sym, B, args.dtype)
-    roofline["traffic"] = traffic
-    roofline["traffic_note"] = ("PMC bytes per launch of the kernel symbol (all call sites; rocprofv3 cannot split "
-                                "them)" if roofline["kernel_all_sites"] and roofline["kernel_all_sites"]["sites"] > 1
-                                else "PMC bytes per launch")
-    if traffic_src:
-        roofline["traffic_source"] = traffic_src
-    roofline["step"] = {"achieved_tflops": round(step_tf, 2), "peak": peak_mfma, "frac": round(step_tf / peak_mfma, 4),
-                        "basis": "essential FLOPs per step (SURVEY.md §8(d): 256.5 GFLOP per segment x 4 stems) / "
-                                 "timed ms per step"}
+    roofline = None
+    if args.full:
+        roofline = roofline_of(model, fwd_only, dominant, peak_mfma, ms, sites, sections=not args.no_extras)
+        kernel_sym = roofline["kernel"]
+        traffic, traffic_src = pmc_traffic(kernel_sym, B, args.dtype)
+        roofline["traffic"] = traffic
+        roofline["traffic_note"] = ("PMC bytes per launch of the kernel symbol (all call sites; rocprofv3 cannot "
+                                    "split them)"
+                                    if roofline["kernel_all_sites"] and roofline["kernel_all_sites"]["sites"] > 1
+                                    else "PMC bytes per launch")
+        if traffic_src:
+            roofline["traffic_source"] = traffic_src
+        roofline["step"] = {"achieved_tflops": round(step_tf, 2), "peak": peak_mfma,
+                            "frac": round(step_tf / peak_mfma, 4),
+                            "basis": "essential FLOPs per step (SURVEY.md §8(d): 256.5 GFLOP per segment x 4 stems) / "
+                                     "timed ms per step"}
     rec = {
         "metric": "6s-segments/sec (each separated into 4 stems; encode once, decode 4x)",
         "value": round(value, 3),
@@ -489,11 +544,12 @@ def main():
                               if graphs else "eager"),
                    "pipelines": len(pipes) + 1, "decode_items": dec_items},
         "stems_per_s": round(4 * value, 3),
-        "roofline": roofline,
         "step_essential_tflops": round(step_tf, 2),
         "workspace_gb": round(ws_bytes / 1e9, 2),
     }
-    if rank == 0 and not args.no_extras:
+    if roofline is not None:
+        rec["roofline"] = roofline
+    if args.full and rank == 0 and not args.no_extras:
         full = torch.zeros((B, len(STEMS), 2, SEG), dtype=torch.float32)
         full[[0, B - 1]] = timed_rows.cpu()
         rec["sdr_db_vs_oracle"] = sdr_vs_oracle(full, sd, table, wav.cpu(), rows=(0, B - 1))
@@ -507,7 +563,7 @@ def main():
             rec["sdr_delta_benchmark_protocol"] = sdr_delta_split(model, m32)
             del m32
             torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         rec["cpu_baseline"] = cpu_baseline(sd, table)
     if rank == 0:
         print(json.dumps(rec), flush=True)

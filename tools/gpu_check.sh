@@ -6,5 +6,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v -rA -p no:cacheprovider
 rc=$?; grep -E "passed|failed" $O/pytest_gpu.log | tail -2
 if [ $rc -ne 0 ]; then grep -E "FAILED|Error|error" $O/pytest_gpu.log | head -20; tail -30 $O/pytest_gpu.log; exit $rc; fi
 cp $O/parity_report.json $O/parity_report_check.json 2>/dev/null
-timeout -k 10 600 python bench.py ${BENCH_ARGS} > $O/bench_full.log 2>&1 || { tail -20 $O/bench_full.log; exit 1; }
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS} > $O/bench_full.log 2>&1 || { tail -20 $O/bench_full.log; exit 1; }
 tail -1 $O/bench_full.log

@@ -13,8 +13,8 @@ echo "== smoke"
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke_$TAG.txt 2>&1 || { tail -20 $O/smoke_$TAG.txt; exit 1; }
 grep smoke $O/smoke_$TAG.txt
 echo "== bench"
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_full.log 2>&1 || { tail -20 $O/bench_full.log; exit 1; }
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_full.log 2>&1 || { tail -20 $O/bench_full.log; exit 1; }
 tail -1 $O/bench_full.log | cut -c1-300
 echo "== sites"
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-extras --dump-kernels $O/kernels_$TAG.json > $O/bench_kernels_$TAG.log 2>&1 || { tail -20 $O/bench_kernels_$TAG.log; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extras --dump-kernels $O/kernels_$TAG.json > $O/bench_kernels_$TAG.log 2>&1 || { tail -20 $O/bench_kernels_$TAG.log; exit 1; }
 tail -1 $O/bench_kernels_$TAG.log | cut -c1-200

@@ -5,7 +5,7 @@ T=${1:-r02}
 O=gpurun_out/pmc_$T
 mkdir -p $O
 export TMPDIR=/tmp
-B="python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras"
+B="python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras"
 run() { timeout -s KILL 240 rocprofv3 --pmc $2 --output-format csv -d $O/$1 -o run -- $B > $O/$1.log 2>&1 || { tail -5 $O/$1.log; exit 1; }; }
 run sqa "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"
 run sqb "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES SQ_INSTS_SALU SQ_INSTS_MFMA SQ_BUSY_CYCLES"

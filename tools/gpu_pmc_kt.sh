@@ -3,7 +3,7 @@
 O=gpurun_out/pmckt_${2:-x}
 mkdir -p $O
 export TMPDIR=/tmp
-B="python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras"
+B="python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras"
 timeout -s KILL 240 rocprofv3 --kernel-include-regex "$1" --pmc FETCH_SIZE --output-format csv -d $O/f -o run -- $B > $O/f.log 2>&1 || { tail -5 $O/f.log; exit 1; }
 timeout -s KILL 240 rocprofv3 --kernel-include-regex "$1" --pmc WRITE_SIZE --output-format csv -d $O/w -o run -- $B > $O/w.log 2>&1 || { tail -5 $O/w.log; exit 1; }
 python - $O <<'PY'

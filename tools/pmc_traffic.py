@@ -11,7 +11,7 @@ are both recorded.
 
     python tools/pmc_traffic.py <fetch_dir> <write_dir> --batch B --dtype bf16 [--calib C] [--widths W]
                                 [--kernels bench_kernels.json] [-o profiles/pmc_traffic.json]
---kernels (bench.py --dump-kernels output): also record each kernel's algorithmic bytes per launch and the ratio
+--kernels (bench.py --full --dump-kernels output): also record each kernel's algorithmic bytes per launch and the ratio
 corrected / algorithmic (below ~0.95 flags an accounting problem: cold reads cannot undercut the algorithmic bytes).
 
 Writes {"batch", "dtype", "correction", "kernels": {label: {"launches", "fetch_kib", "write_kib",

@@ -4,11 +4,13 @@
 set -o pipefail
 export TMPDIR=/tmp
 TAG=$1; N=$2; shift 2
+O=${ATHD_OUT:-bench_out}
+mkdir -p $O
 for i in $(seq $N); do
   for L in "$@"; do
     n=$(basename $L .so)
-    ATHD_LIB=$(realpath $L) timeout -k 10 300 python bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 5 --dump-kernels gpurun_out/${TAG}_k_${n}_$i.json > gpurun_out/${TAG}_b_${n}_$i.log 2>&1 || { tail -5 gpurun_out/${TAG}_b_${n}_$i.log; exit 1; }
-    python - "$n" gpurun_out/${TAG}_k_${n}_${i}_sites.json gpurun_out/${TAG}_b_${n}_$i.log "${AB_GREP:-attn}" <<'PY'
+    ATHD_LIB=$(realpath $L) timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extras --steps 20 --warmup 5 --dump-kernels $O/${TAG}_k_${n}_$i.json > $O/${TAG}_b_${n}_$i.log 2>&1 || { tail -5 $O/${TAG}_b_${n}_$i.log; exit 1; }
+    python - "$n" $O/${TAG}_k_${n}_${i}_sites.json $O/${TAG}_b_${n}_$i.log "${AB_GREP:-attn}" <<'PY'
 import json, sys
 n, kf, bf, pat = sys.argv[1:5]
 ks = json.load(open(kf))

@@ -2,12 +2,14 @@
 set -o pipefail
 export TMPDIR=/tmp
 TAG=$1; N=$2; shift 2
+O=${ATHD_OUT:-bench_out}
+mkdir -p $O
 for i in $(seq $N); do
   k=0
   for E in "$@"; do
     k=$((k+1))
-    env $E timeout -k 10 300 python bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 5 --dump-kernels gpurun_out/${TAG}_k_${k}_$i.json > gpurun_out/${TAG}_b_${k}_$i.log 2>&1 || { tail -5 gpurun_out/${TAG}_b_${k}_$i.log; exit 1; }
-    python - "$E" gpurun_out/${TAG}_k_${k}_${i}_sites.json gpurun_out/${TAG}_b_${k}_$i.log "${AB_GREP:-attn}" <<'PY'
+    env $E timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extras --steps 20 --warmup 5 --dump-kernels $O/${TAG}_k_${k}_$i.json > $O/${TAG}_b_${k}_$i.log 2>&1 || { tail -5 $O/${TAG}_b_${k}_$i.log; exit 1; }
+    python - "$E" $O/${TAG}_k_${k}_${i}_sites.json $O/${TAG}_b_${k}_$i.log "${AB_GREP:-attn}" <<'PY'
 import json, sys
 n, kf, bf, pat = sys.argv[1:5]
 ks = json.load(open(kf))

@@ -1,4 +1,4 @@
-"""Compare two per-call-site kernel time dumps (bench.py --dump-kernels X.json -> X_sites.json).
+"""Compare two per-call-site kernel time dumps (bench.py --full --dump-kernels X.json -> X_sites.json).
 
     python tools/sites_diff.py OLD_sites.json NEW_sites.json [-n 20]
 """
