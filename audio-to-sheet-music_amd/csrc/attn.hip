@@ -1301,7 +1301,9 @@ static bool attn32_ok(const AttnDesc& d, int mode) {
     return attn_variant() != 1 && mode == 1 && d.q_bf16 && d.k_bf16 && d.v_bf16 && d.o_bf16 &&
            fabsf(d.scale * 1.4426950408889634f - 1.f) < 1e-6f && d.q_ld % 8 == 0 && d.k_ld % 8 == 0 &&
            d.v_ld % 8 == 0 && d.o_ld % 8 == 0 && d.q_off % 8 == 0 && d.k_off % 8 == 0 && d.v_off % 8 == 0 &&
-           d.Nq > 0 && d.Nk > 0;
+           d.Nq > 0 && d.Nk > 0 &&
+           // the LDS-DMA staging's per-lane byte offsets (key row in the tile x row pitch) are 24-bit multiplies
+           d.k_ld > 0 && d.v_ld > 0 && (int64_t)d.k_ld * 2 < (1 << 24) && (int64_t)d.v_ld * 2 < (1 << 24);
 }
 
 // ATHD_ATTN_PP=1/2/3: the bf16 path on attn_pp_kernel<1/0/2> (A/B; read at every launch)

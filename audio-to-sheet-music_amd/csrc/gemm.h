@@ -131,8 +131,33 @@ inline void gemm_work(const GemmDesc& d, int mode, double& flops, double& bytes)
     if (d.pbias) bytes += (double)d.nb * (d.pfold > 1 ? d.pfold : 1) * d.N * 4;
 }
 
+// The kernel family gemm_launch runs a descriptor on (gemm_route; the kernel tests record it for every case).
+enum GemmRoute {
+    ROUTE_REFUSED = 0,   // gemm_launch returns -2 without launching
+    ROUTE_ROWLN,         // rowln.hip: residual projection + the next LayerNorm (ln_out)
+    ROUTE_ROWLN_TEXT,    // rowln.hip: the text mlp2 + norm_out (ATHD_RLT != 0)
+    ROUTE_GEMM3_LN,      // gemm3.hip: 128 x 384 tiles with the row-LayerNorm epilogue
+    ROUTE_GEMM2_AGN,     // gemm2.hip with the GroupNorm folded into the f32 A load
+    ROUTE_GEMM5,         // gemm5.hip: 256 x 256 tiles
+    ROUTE_GEMM3_V3,      // gemm3.hip: 256 x 192 tiles, 2 stages (K < 384)
+    ROUTE_GEMM3_V7,      // gemm3.hip: 192 x 192 tiles, 3 stages
+    ROUTE_GEMM2,         // gemm2.hip
+    ROUTE_V1_BF16,       // gemm.hip, bf16 MFMA
+    ROUTE_V1_F32         // gemm.hip, fp32 MFMA (f32 parity mode)
+};
+
 // mode: 0 = exact fp32 (v_mfma_f32_16x16x4_f32), 1 = bf16 (v_mfma_f32_16x16x32_bf16, fp32 accumulate)
 int gemm_launch(const GemmDesc& d, int mode, hipStream_t s);
+// the GemmRoute gemm_launch takes for d (reads ATHD_RLT as gemm_launch does)
+int gemm_route(const GemmDesc& d, int mode);
+// Split-K tail of gemm5's dense residual-stream launches (gemm5.hip launch5f): with R resident one-tile blocks per
+// round, the first `full` tiles are computed whole and the `tail` tiles of the last, partial round in S K pieces each
+// (S == 1, tail == 0: no split).  gemm5_sk_resident: R of the kernel d runs on, 0 when that launch form never splits.
+struct SkPlan {
+    int full, tail, S;
+};
+SkPlan gemm5_sk_plan(const GemmDesc& d, int64_t R);
+int64_t gemm5_sk_resident(const GemmDesc& d);
 // the shapes the residual projection + LayerNorm pass (rowln.hip, GemmDesc::ln_out) handles
 bool rowln_supported(const GemmDesc& d);
 // d with its fast-division constants filled (every kernel launcher passes this copy to the kernel)

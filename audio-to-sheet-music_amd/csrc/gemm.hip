@@ -281,6 +281,7 @@ bool gemm2_supported(const GemmDesc& d);
 int gemm2_launch(const GemmDesc& d, hipStream_t s);
 bool gemm3_supported(const GemmDesc& d);
 int gemm3_launch(const GemmDesc& d, hipStream_t s, int variant);
+bool gemm3_ln_supported(const GemmDesc& d);
 int gemm3_ln_launch(const GemmDesc& d, hipStream_t s);
 bool gemm5_supported(const GemmDesc& d);
 int gemm5_launch(const GemmDesc& d, hipStream_t s);
@@ -288,54 +289,64 @@ int gemm5_launch(const GemmDesc& d, hipStream_t s);
 bool rowln_supported(const GemmDesc& d);
 int rowln_launch(const GemmDesc& d, hipStream_t s);
 bool rowln_text_enabled();
+bool rowln_text_supported(const GemmDesc& d);
 int rowln_text_launch(const GemmDesc& d, hipStream_t s);
 #ifdef ATHD_KBENCH
 int gemm6_launch(const GemmDesc& d, hipStream_t s);
 #endif
 
-int gemm_launch(const GemmDesc& d0, int mode, hipStream_t s) {
-    if (d0.Kp % BK != 0 || d0.Kp < d0.K || d0.C_in <= 0 || d0.N <= 0) return -2;
-    const GemmDesc d = with_fastdiv(d0);
-    if (d.act == ACT_GLU && (d.N % 32 != 0)) return -2;
+// The dispatch of gemm_launch as a pure function of the descriptor (and ATHD_RLT): the route, or ROUTE_REFUSED.
+int gemm_route(const GemmDesc& d, int mode) {
+    if (d.Kp % BK != 0 || d.Kp < d.K || d.C_in <= 0 || d.N <= 0) return ROUTE_REFUSED;
+    if (d.act == ACT_GLU && (d.N % 32 != 0)) return ROUTE_REFUSED;
     // residual projection + the next LayerNorm (rowln.hip), bf16 mode only
-    if (d.ln_out) return mode == 1 && rowln_supported(d) ? rowln_launch(d, s) : -2;
+    if (d.ln_out) return mode == 1 && rowln_supported(d) ? ROUTE_ROWLN : ROUTE_REFUSED;
     // row-LayerNorm epilogue (the text mlp2): rowln.hip's text form, else gemm3
     if (d.ln_w) {
-        if (mode != 1) return -2;
-        if (rowln_text_enabled()) {
-            const int rc = rowln_text_launch(d, s);
-            if (rc != -2) return rc;
-        }
-        return gemm3_ln_launch(d, s);
+        if (mode != 1) return ROUTE_REFUSED;
+        if (rowln_text_enabled() && rowln_text_supported(d)) return ROUTE_ROWLN_TEXT;
+        return gemm3_ln_supported(d) ? ROUTE_GEMM3_LN : ROUTE_REFUSED;
     }
     // the GroupNorm folded into the A load (a_gn_*, the transformer's last pending GroupNorm): gemm2 only; refuse
     // rather than silently skip it on another kernel
-    if (d.a_gn_stats) return mode == 1 && gemm2_supported(d) ? gemm2_launch(d, s) : -2;
+    if (d.a_gn_stats) return mode == 1 && gemm2_supported(d) ? ROUTE_GEMM2_AGN : ROUTE_REFUSED;
     // the residual's GroupNorm (res_gn_*): gemm5's residual epilogue only
-    if (d.res_gn_stats && !(mode == 1 && gemm5_supported(d) && d.N % 256 == 0 && epi_res_fast_ok(d))) return -2;
+    if (d.res_gn_stats && !(mode == 1 && gemm5_supported(d) && d.N % 256 == 0 && epi_res_fast_ok(d))) return ROUTE_REFUSED;
     // bf16 activations, N a multiple of 256: 256x256 tile, staggered two-group K-loop (gemm5.hip; it replaced round
     // 2's gemm4.hip, which tools/kbench still builds as the A/B baseline: kbench +6..16 % on the transformer shapes,
     // equal at K = 2048).  (Measured on N = 192 / 384: slower than gemm3's 256x192 tiles, which waste no columns.)
+    if (mode == 1 && gemm5_supported(d) && d.N % 256 == 0) return ROUTE_GEMM5;
+    // other N >= 192: 256x192 or 192x192 tile, 8 waves (gemm3.hip)
+    // (K >= 384: 192x192 tiles with a 3-stage ring, two K-tiles in flight across each barrier; measured per call
+    // site 2-20 % faster there.  Shorter K, e.g. the K=288 four-residue ConvT, keeps 256x192 x 2 stages.)
+    if (mode == 1 && gemm3_supported(d) && d.N >= 192) return d.K >= 384 ? ROUTE_GEMM3_V7 : ROUTE_GEMM3_V3;
+    if (mode == 1 && gemm2_supported(d)) return ROUTE_GEMM2;
+    return mode == 1 ? ROUTE_V1_BF16 : ROUTE_V1_F32;
+}
+
+int gemm_launch(const GemmDesc& d0, int mode, hipStream_t s) {
+    const GemmDesc d = with_fastdiv(d0);
 #ifdef ATHD_KBENCH
     // dense linear rows without a residual epilogue, B from L2 (gemm6.hip, round-5 experiment, measured slower than
     // gemm5: built into tools/libkbench.so only, with ATHD_G6=1; -2 otherwise or when the shape is not its)
-    if (mode == 1) {
+    if (mode == 1 && gemm_route(d, mode) >= ROUTE_GEMM5) {
         const int rc = gemm6_launch(d, s);
         if (rc != -2) return rc;
     }
 #endif
-    if (mode == 1 && gemm5_supported(d) && d.N % 256 == 0) return gemm5_launch(d, s);
-    // other N >= 192: 256x192 or 192x192 tile, 8 waves (gemm3.hip)
-    // (K >= 384: 192x192 tiles with a 3-stage ring, two K-tiles in flight across each barrier; measured per call
-    // site 2-20 % faster there.  Shorter K, e.g. the K=288 four-residue ConvT, keeps 256x192 x 2 stages.)
-    if (mode == 1 && gemm3_supported(d) && d.N >= 192) {
-        const int v = d.K >= 384 ? 7 : 3;
-        return gemm3_launch(d, s, 100 + v);               // persistent grid
+    switch (gemm_route(d, mode)) {
+        case ROUTE_ROWLN: return rowln_launch(d, s);
+        case ROUTE_ROWLN_TEXT: return rowln_text_launch(d, s);
+        case ROUTE_GEMM3_LN: return gemm3_ln_launch(d, s);
+        case ROUTE_GEMM2_AGN:
+        case ROUTE_GEMM2: return gemm2_launch(d, s);
+        case ROUTE_GEMM5: return gemm5_launch(d, s);
+        case ROUTE_GEMM3_V3: return gemm3_launch(d, s, 100 + 3);          // persistent grid
+        case ROUTE_GEMM3_V7: return gemm3_launch(d, s, 100 + 7);
+        case ROUTE_V1_BF16: launch_mode<1>(d, s); return (int)hipGetLastError();
+        case ROUTE_V1_F32: launch_mode<0>(d, s); return (int)hipGetLastError();
+        default: return -2;
     }
-    if (mode == 1 && gemm2_supported(d)) return gemm2_launch(d, s);
-    if (mode == 1) launch_mode<1>(d, s);
-    else launch_mode<0>(d, s);
-    return (int)hipGetLastError();
 }
 
 }  // namespace athd

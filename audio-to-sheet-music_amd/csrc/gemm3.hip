@@ -340,9 +340,12 @@ static constexpr unsigned F_TEXT_LN = F_RES | F_PB | F_LN | F_CBF16;
 // 4 = 128x192 (4 waves, 2 stages: 80 KB LDS, 2 blocks/CU), 5 = 128x192 (4 waves, 3 stages), 6 = 128x96 (4 waves, 3 st),
 // 7 = 192x192 (8 waves, 3 stages: 144 KB LDS), 8 = 128x192 (8 waves, 2 stages: 80 KB, 2 blocks/CU); + 100: persistent
 // grid (resident blocks walk the M tiles)
+bool gemm3_ln_supported(const GemmDesc& d) {
+    return !(epi_flags(d) != F_TEXT_LN || d.N != 384 || !gemm3_supported(d) || d.ldo != 384 || d.res_bf16 || d.col_off != 0);
+}
+
 int gemm3_ln_launch(const GemmDesc& d, hipStream_t s) {
-    if (epi_flags(d) != F_TEXT_LN || d.N != 384 || !gemm3_supported(d) || d.ldo != 384 || d.res_bf16 || d.col_off != 0)
-        return -2;
+    if (!gemm3_ln_supported(d)) return -2;
     launch3f<128, 384, 2, 4, 2, F_TEXT_LN>(d, s, true);
     return (int)hipGetLastError();
 }

@@ -498,6 +498,47 @@ bool gemm5_supported(const GemmDesc& d) {
            d.col_split % 4 == 0 && (d.act != ACT_GLU || d.N % 32 == 0);
 }
 
+// the launch forms with a split-K tail: one-tile blocks (not persistent), dense rows, the residual-stream epilogues
+template <unsigned F, bool LIN>
+static constexpr bool sk_form() {
+    return !g5_persist(F) && LIN && (F == (F_RES | F_STATS) || F == F_RES);
+}
+
+// resident blocks of one round of gemm5_kernel<F, PROBE, LIN> on the current device (0: unknown)
+template <unsigned F, int PROBE, bool LIN>
+static int64_t sk_resident() {
+    static int per_cu = 0;   // a property of the kernel; the CU count is the current device's
+    if (per_cu == 0) {
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm5_kernel<F, PROBE, LIN>, 512, 0);
+        if (per_cu <= 0) per_cu = -1;
+    }
+    return per_cu > 0 ? (int64_t)per_cu * device_cus() : 0;
+}
+
+// Split-K tail: a grid of `tiles` one-tile blocks at R resident blocks runs ceil(tiles / R) rounds; the last
+// round's `tail` tiles (e.g. linear2: 1036 = 4 x 256 + 12) leave the other CUs idle for a whole tile time.
+// Those tiles are cut into S K pieces each (>= 4 K-tiles), computed as extra blocks of the same launch, and
+// added up by gemm5_sk_reduce_kernel, which also runs their epilogue.  (H_out * W >= 4: a reduce block's 4 rows
+// span at most two batches, gemm5_sk_reduce_kernel's statistics.)
+SkPlan gemm5_sk_plan(const GemmDesc& d, int64_t R) {
+    const int64_t M = (int64_t)d.nb * d.H_out * d.W;
+    const int64_t tiles = ((M + 255) / 256) * ((d.N + 255) / 256);
+    SkPlan p{(int)tiles, 0, 1};
+    const int nkt = d.Kp / 64;
+    const int64_t tail = R > 0 ? tiles % R : 0;
+    if (d.sk_ws && epi_res_fast_ok(d) && (int64_t)d.H_out * d.W >= 4 && tiles > R && tail > 0 && 2 * tail <= R &&
+        nkt >= 8) {
+        int S = (int)std::min<int64_t>(std::min<int64_t>(R / tail, nkt / 4), SK_MAX_S);
+        S = std::min<int64_t>(S, SK_MAX_PIECES / tail);
+        if (S >= 2) {
+            p.full = (int)(tiles - tail);
+            p.tail = (int)tail;
+            p.S = S;
+        }
+    }
+    return p;
+}
+
 template <unsigned F, int PROBE = 0, bool LIN = false>
 static void launch5f(const GemmDesc& d, hipStream_t s) {
     const int64_t M = (int64_t)d.nb * d.H_out * d.W;
@@ -514,28 +555,13 @@ static void launch5f(const GemmDesc& d, hipStream_t s) {
     }
     GemmDesc e = with_fastdiv(d);
     int sk_tail = 0;
-    if constexpr (!g5_persist(F) && LIN && (F == (F_RES | F_STATS) || F == F_RES)) {
-        // split-K tail: a grid of `tiles` one-tile blocks at one block per CU runs ceil(tiles / R) rounds; the last
-        // round's `tail` tiles (e.g. linear2: 1036 = 4 x 256 + 12) leave the other CUs idle for a whole tile time.
-        // Those tiles are cut into S K pieces each (>= 4 K-tiles), computed as extra blocks of the same launch, and
-        // added up by gemm5_sk_reduce_kernel, which also runs their epilogue.
-        static int per_cu = 0;
-        if (per_cu == 0) {
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm5_kernel<F, PROBE, LIN>, 512, 0);
-            if (per_cu <= 0) per_cu = -1;
-        }
-        const int64_t R = per_cu > 0 ? (int64_t)per_cu * device_cus() : 0;
-        const int nkt = d.Kp / 64;
-        const int64_t tail = R > 0 ? tiles % R : 0;
-        if (d.sk_ws && epi_res_fast_ok(d) && tiles > R && tail > 0 && 2 * tail <= R && nkt >= 8) {
-            int S = (int)std::min<int64_t>(std::min<int64_t>(R / tail, nkt / 4), SK_MAX_S);
-            S = std::min<int64_t>(S, SK_MAX_PIECES / tail);
-            if (S >= 2) {
-                e.sk_full = (int)(tiles - tail);
-                e.sk_S = S;
-                grid = e.sk_full + tail * S;
-                sk_tail = (int)tail;
-            }
+    if constexpr (sk_form<F, LIN>()) {
+        const SkPlan p = gemm5_sk_plan(d, sk_resident<F, PROBE, LIN>());
+        if (p.S >= 2) {
+            e.sk_full = p.full;
+            e.sk_S = p.S;
+            grid = p.full + (int64_t)p.tail * p.S;
+            sk_tail = p.tail;
         }
     }
     if (!sk_tail) e.sk_ws = nullptr;
@@ -565,6 +591,14 @@ static bool gemm5_lin(const GemmDesc& d) {
 #ifndef ATHD_G5_LIN
 #define ATHD_G5_LIN 1       // (0: every launch takes the general implicit-GEMM addressing; kbench A/B builds)
 #endif
+
+int64_t gemm5_sk_resident(const GemmDesc& d) {
+    if (!(ATHD_G5_LIN && gemm5_lin(d))) return 0;
+    const unsigned f = epi_flags(d);
+    if (f == (F_RES | F_STATS)) return sk_form<F_RES | F_STATS, true>() ? sk_resident<F_RES | F_STATS, 0, true>() : 0;
+    if (f == F_RES) return sk_form<F_RES, true>() ? sk_resident<F_RES, 0, true>() : 0;
+    return 0;
+}
 
 int gemm5_launch(const GemmDesc& d, hipStream_t s) {
     const bool lin = ATHD_G5_LIN && gemm5_lin(d);

@@ -36,7 +36,7 @@ inline int64_t istft_ola_part_floats(int64_t NI, int Tspec) { return NI * istft_
 // norm.hip
 // per-batch {sum, sumsq} (double) of x[b][0..n)
 void stats_launch(const float* x, int nb, int64_t n, double* stats, hipStream_t s);
-// input normalisation: per batch (mean, 1/(1e-5 + unbiased std)) as floats {mean, inv} and (mean, std)
+// input normalisation: per batch (mean, 1e-5 + unbiased std) as floats {sub, div} (GemmDesc::a_norm) and (mean, std)
 void input_norm_params_launch(const double* stats, int nb, int64_t n, float* mean_inv, float* mean_std,
                               hipStream_t s);
 // h[nb][L*H] = GELU(GN(h)) in place (GroupNorm(1,H), stats over L*H per nb)

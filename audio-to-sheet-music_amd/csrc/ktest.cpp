@@ -1,0 +1,143 @@
+// Test entries for the kernel launchers (libathd_ktest.so, tests/ktest.py).  No kernels here: every kt_* wrapper copies
+// a flat descriptor of int64_t / pointer fields into the launcher's own descriptor and calls the launcher that
+// libathd.so ships.  Not part of the product ABI (include/athd.h).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "attn.h"
+#include "gemm.h"
+#include "kernels.h"
+
+using namespace athd;
+
+extern "C" {
+
+struct KtGemm {
+    void* A; int64_t a_bf16, nb, H_in, W, C_in, a_ld, a_cs, a_bs, a_hs, ntaps, in_stride, in_off, dil, H_out;
+    void* a_norm; void* a_gn_stats; int64_t a_gn_count; void* a_gn_w; void* a_gn_b;
+    void* Wp; int64_t N, K, Kp; void* bias;
+    void* C; int64_t c_bf16, H_out_total, o_stride, o_off, ldo, col_off, c_bs, store; void* c4;
+    int64_t col_split, hi_row_off, store_mask, k_blk, act;
+    void* res; int64_t res_bf16; void* res_scale; void* res_gn_stats; int64_t res_gn_count; void* res_gn_w; void* res_gn_b;
+    void* row_add; void* stats; void* gn_stats; int64_t gn_count; void* gn_w; void* gn_b;
+    void* pbias; int64_t pfold, res_div, res_bs;
+    void* ln_w; void* ln_b; void* ln_out; void* sk_ws;
+};
+
+struct KtAttn {
+    void* Q; int64_t q_bf16, q_bs, q_ld, q_off;
+    void* K; int64_t k_bf16, k_bs, k_ld, k_off;
+    void* V; int64_t v_bf16, v_bs, v_ld, v_off;
+    void* O; int64_t o_bf16, o_bs, o_ld;
+    int64_t nb, Nq, Nk, heads;
+    int64_t scale_bits;      // the f32 scale's bit pattern
+};
+
+struct KtLn {
+    void* x; int64_t nb, N, C; void* w; void* b; void* gn_stats; void* gn_w; void* gn_b; int64_t gn_writeback;
+    void* pos; void* out; int64_t out_bf16; void* w2; void* b2; void* out2;
+};
+
+struct KtConvT4 {
+    void* x; void* w; void* bias; void* out; void* stats; int64_t nb, H, W, keep;
+};
+
+int64_t kt_sizeof_gemm() { return (int64_t)sizeof(KtGemm); }
+int64_t kt_sizeof_attn() { return (int64_t)sizeof(KtAttn); }
+int64_t kt_sizeof_ln() { return (int64_t)sizeof(KtLn); }
+int64_t kt_sizeof_convt4() { return (int64_t)sizeof(KtConvT4); }
+
+static GemmDesc to_desc(const KtGemm* k) {
+    GemmDesc g;
+    g.A = k->A; g.a_bf16 = (int)k->a_bf16; g.nb = (int)k->nb; g.H_in = (int)k->H_in; g.W = (int)k->W;
+    g.C_in = (int)k->C_in; g.a_ld = (int)k->a_ld; g.a_cs = k->a_cs; g.a_bs = k->a_bs; g.a_hs = k->a_hs;
+    g.ntaps = (int)k->ntaps; g.in_stride = (int)k->in_stride; g.in_off = (int)k->in_off; g.dil = (int)k->dil;
+    g.H_out = (int)k->H_out;
+    g.a_norm = (const float*)k->a_norm; g.a_gn_stats = (const double*)k->a_gn_stats; g.a_gn_count = k->a_gn_count;
+    g.a_gn_w = (const float*)k->a_gn_w; g.a_gn_b = (const float*)k->a_gn_b;
+    g.Wp = k->Wp; g.N = (int)k->N; g.K = (int)k->K; g.Kp = (int)k->Kp; g.bias = (const float*)k->bias;
+    g.C = k->C; g.c_bf16 = (int)k->c_bf16; g.H_out_total = (int)k->H_out_total; g.o_stride = (int)k->o_stride;
+    g.o_off = (int)k->o_off; g.ldo = (int)k->ldo; g.col_off = (int)k->col_off; g.c_bs = k->c_bs;
+    g.store = (int)k->store; g.c4 = k->c4;
+    g.col_split = (int)k->col_split; g.hi_row_off = (int)k->hi_row_off; g.store_mask = (int)k->store_mask;
+    g.k_blk = (int)k->k_blk; g.act = (int)k->act;
+    g.res = k->res; g.res_bf16 = (int)k->res_bf16; g.res_scale = (const float*)k->res_scale;
+    g.res_gn_stats = (const double*)k->res_gn_stats; g.res_gn_count = k->res_gn_count;
+    g.res_gn_w = (const float*)k->res_gn_w; g.res_gn_b = (const float*)k->res_gn_b;
+    g.row_add = (const float*)k->row_add; g.stats = (double*)k->stats; g.gn_stats = (const double*)k->gn_stats;
+    g.gn_count = k->gn_count; g.gn_w = (const float*)k->gn_w; g.gn_b = (const float*)k->gn_b;
+    g.pbias = (const float*)k->pbias; g.pfold = (int)k->pfold; g.res_div = (int)k->res_div; g.res_bs = k->res_bs;
+    g.ln_w = (const float*)k->ln_w; g.ln_b = (const float*)k->ln_b; g.ln_out = k->ln_out; g.sk_ws = (float*)k->sk_ws;
+    return g;
+}
+
+int kt_gemm(const KtGemm* k, int mode, void* stream) { return gemm_launch(to_desc(k), mode, (hipStream_t)stream); }
+int kt_gemm_route(const KtGemm* k, int mode) { return gemm_route(to_desc(k), mode); }
+int64_t kt_sk_bytes() { return (int64_t)SK_WS_BYTES; }
+int64_t kt_sk_resident(const KtGemm* k) { return gemm5_sk_resident(to_desc(k)); }
+// out = {full, tail, S} of the launch gemm_launch would make for k (no split when the route is not gemm5's)
+void kt_sk_plan(const KtGemm* k, int64_t* out) {
+    const GemmDesc g = to_desc(k);
+    SkPlan p = gemm5_sk_plan(g, gemm_route(g, 1) == ROUTE_GEMM5 ? gemm5_sk_resident(g) : 0);
+    out[0] = p.full; out[1] = p.tail; out[2] = p.S;
+}
+
+int kt_attn(const KtAttn* k, int mode, void* stream) {
+    AttnDesc a;
+    a.Q = k->Q; a.q_bf16 = (int)k->q_bf16; a.q_bs = k->q_bs; a.q_ld = (int)k->q_ld; a.q_off = (int)k->q_off;
+    a.K = k->K; a.k_bf16 = (int)k->k_bf16; a.k_bs = k->k_bs; a.k_ld = (int)k->k_ld; a.k_off = (int)k->k_off;
+    a.V = k->V; a.v_bf16 = (int)k->v_bf16; a.v_bs = k->v_bs; a.v_ld = (int)k->v_ld; a.v_off = (int)k->v_off;
+    a.O = k->O; a.o_bf16 = (int)k->o_bf16; a.o_bs = k->o_bs; a.o_ld = (int)k->o_ld;
+    a.nb = (int)k->nb; a.Nq = (int)k->Nq; a.Nk = (int)k->Nk; a.heads = (int)k->heads;
+    const uint32_t bits = (uint32_t)k->scale_bits;
+    memcpy(&a.scale, &bits, 4);
+    return attn_launch(a, mode, (hipStream_t)stream);
+}
+
+int kt_layernorm(const KtLn* k, void* stream) {
+    LnDesc l;
+    l.x = (float*)k->x; l.nb = (int)k->nb; l.N = k->N; l.C = (int)k->C; l.w = (const float*)k->w; l.b = (const float*)k->b;
+    l.gn_stats = (const double*)k->gn_stats; l.gn_w = (const float*)k->gn_w; l.gn_b = (const float*)k->gn_b;
+    l.gn_writeback = (int)k->gn_writeback; l.pos = (const float*)k->pos; l.out = k->out; l.out_bf16 = (int)k->out_bf16;
+    l.w2 = (const float*)k->w2; l.b2 = (const float*)k->b2; l.out2 = k->out2;
+    layernorm_launch(l, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+int kt_convt4(const KtConvT4* k, void* stream) {
+    ConvT4Desc c;
+    c.x = (const uint16_t*)k->x; c.w = (const uint16_t*)k->w; c.bias = (const float*)k->bias; c.out = (uint16_t*)k->out;
+    c.stats = (double*)k->stats; c.nb = (int)k->nb; c.H = (int)k->H; c.W = (int)k->W; c.keep = (int)k->keep;
+    return convt4_launch(c, (hipStream_t)stream);
+}
+
+int kt_to_bf16(const float* x, uint16_t* y, int64_t n, void* stream) {
+    to_bf16_launch(x, y, n, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+int kt_stats(const float* x, int64_t nb, int64_t n, double* stats, void* stream) {
+    stats_launch(x, (int)nb, n, stats, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+int kt_input_norm_params(const double* stats, int64_t nb, int64_t n, float* mean_inv, float* mean_std, void* stream) {
+    input_norm_params_launch(stats, (int)nb, n, mean_inv, mean_std, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+int kt_gn_gelu(float* h, int64_t nb, int64_t per_batch, int64_t H, const double* stats, const float* w, const float* b,
+               int64_t fast, void* stream) {
+    gn_gelu_launch(h, (int)nb, per_batch, (int)H, stats, w, b, (hipStream_t)stream, fast != 0);
+    return (int)hipGetLastError();
+}
+int kt_gn_gelu_bf16(const float* h, uint16_t* out, int64_t nb, int64_t per_batch, int64_t H, const double* stats,
+                    const float* w, const float* b, void* stream) {
+    gn_gelu_bf16_launch(h, out, (int)nb, per_batch, (int)H, stats, w, b, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+int kt_gn_apply(float* x, int64_t nb, int64_t N, int64_t C, const double* stats, const float* w, const float* b,
+                void* stream) {
+    gn_apply_launch(x, (int)nb, N, (int)C, stats, w, b, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"
