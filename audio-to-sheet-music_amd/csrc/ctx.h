@@ -98,6 +98,13 @@ inline std::vector<float> conv1x1_moments(const std::vector<float>& w, const std
     }
     return std::vector<float>(g.begin(), g.end());
 }
+// K order of the rewrite weights that the fused DConv apply multiplies (dconv.hip dconv_apply_kernel<C, NW, true>,
+// C = 48, 96): K slot 32 ks + 8 g + i holds channel 32 ks + 4 g + i (i < 4) or 32 ks + 16 + 4 g + (i - 4), the order in
+// which a lane holds its row's updated channels.  Slots whose channel is >= C are zero.
+inline int dconv_rewrite_perm(int k) {
+    const int ks = k / 32, g = (k % 32) / 8, i = k % 8;
+    return 32 * ks + (i < 4 ? 4 * g + i : 16 + 4 * g + (i - 4));
+}
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t rup(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 constexpr int ENC_CH[4] = {48, 96, 192, 384};

@@ -327,7 +327,7 @@ struct DcApply {
     int64_t M, L, gn_count;
     int kp;
     // fused rewrite (RW, C = 48 / 96, the layer's second DConv layer): out = GLU(Wr x + br) of the updated rows
-    // instead of storing x; rw [2C][rkp] GLU-interleaved rows with the K order of dconv_rewrite_perm
+    // instead of storing x; rw [2C][rkp] GLU-interleaved rows with the K order of ctx.h dconv_rewrite_perm
     const uint16_t* rw = nullptr;
     const float* rbias = nullptr;  // [2C] packed
     uint16_t* out = nullptr;       // [M][C] bf16

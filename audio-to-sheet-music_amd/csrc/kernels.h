@@ -198,7 +198,7 @@ int convt4_launch(const ConvT4Desc& d, hipStream_t s);
 // dconv.hip, bf16 mode, MFMA passes (C = 48, 96, 192, 384): the DConv 1x1 apply x += scale * GLU(GN(W1 hb + b1))
 // (hb [M][HS] with HS = C/8, or 16 for C = 48, 96; x [M][C]; GroupNorm groups of L rows); -1 if the shape is not
 // covered.  With rw (C = 48, 96) the updated rows are not stored: the encoder layer's rewrite out = GLU(Wr x + br)
-// runs on them in registers (rw: [2C][kp] GLU-interleaved rows in the K order of ctx.h rewrite_perm).
+// runs on them in registers (rw: [2C][kp] GLU-interleaved rows in the K order of ctx.h dconv_rewrite_perm).
 struct DcRewrite {
     const uint16_t* w;
     int kp;

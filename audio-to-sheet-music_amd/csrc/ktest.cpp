@@ -6,8 +6,14 @@
 #include <string.h>
 
 #include "attn.h"
+#include "ctx.h"
 #include "gemm.h"
 #include "kernels.h"
+
+namespace athd {   // dconv.hip: the launchers' own shape predicates (no header declares them)
+bool dconv_conv3_supported(int C, int H, int kp, int64_t L);
+bool dconv_apply_supported(int C, int H, int kp, int64_t M);
+}  // namespace athd
 
 using namespace athd;
 
@@ -43,6 +49,36 @@ struct KtConvT4 {
     void* x; void* w; void* bias; void* out; void* stats; int64_t nb, H, W, keep;
 };
 
+struct KtConv3 {
+    void* x; void* w; int64_t kp; void* bias; void* h; void* st; int64_t M, L, C, dil;
+};
+
+struct KtApply {
+    void* hb; void* w; int64_t kp; void* bias; void* st; void* gn_w; void* gn_b; void* scale; void* x; int64_t M, L, C;
+    int64_t rewrite; void* rw_w; int64_t rw_kp; void* rw_bias; void* rw_out; void* rw_c4;
+};
+
+struct KtDcSmall {
+    void* x; int64_t x_bf16; void* h; int64_t nb, L, C, dil; void* w3; void* b3; void* g1w; void* g1b; void* w1; void* b1;
+    void* gram1; void* g2w; void* g2b; void* scale; void* st_h; void* st_y; int64_t fast;
+};
+
+struct KtGnMom {
+    void* h; void* out; int64_t nb, L, H; void* stats; void* w; void* b; void* gram; void* st_y;
+};
+
+struct KtFencRow {
+    void* in; void* a_norm; int64_t B, Fin, Fout, T; void* wc; int64_t wc_ld; void* bc;
+    void* w3[2]; int64_t w3_ld; void* b3[2]; void* g1w[2]; void* g1b[2]; void* w1[2]; int64_t w1_ld; void* b1[2];
+    void* g2w[2]; void* g2b[2]; void* gram[2]; void* scale[2]; void* wr; int64_t wr_ld; void* br; void* row_add;
+    void* out; void* out4; int64_t cin, c;
+};
+
+int64_t kt_sizeof_conv3() { return (int64_t)sizeof(KtConv3); }
+int64_t kt_sizeof_apply() { return (int64_t)sizeof(KtApply); }
+int64_t kt_sizeof_dcsmall() { return (int64_t)sizeof(KtDcSmall); }
+int64_t kt_sizeof_gnmom() { return (int64_t)sizeof(KtGnMom); }
+int64_t kt_sizeof_fencrow() { return (int64_t)sizeof(KtFencRow); }
 int64_t kt_sizeof_gemm() { return (int64_t)sizeof(KtGemm); }
 int64_t kt_sizeof_attn() { return (int64_t)sizeof(KtAttn); }
 int64_t kt_sizeof_ln() { return (int64_t)sizeof(KtLn); }
@@ -134,6 +170,76 @@ int kt_gn_gelu_bf16(const float* h, uint16_t* out, int64_t nb, int64_t per_batch
     gn_gelu_bf16_launch(h, out, (int)nb, per_batch, (int)H, stats, w, b, (hipStream_t)stream);
     return (int)hipGetLastError();
 }
+// ---- the DConv kernels and the fused encoder rows ----
+int kt_dconv_conv3(const KtConv3* k, void* stream) {
+    return dconv_conv3_launch((const uint16_t*)k->x, (const uint16_t*)k->w, (int)k->kp, (const float*)k->bias,
+                              (float*)k->h, (double*)k->st, k->M, k->L, (int)k->C, (int)k->dil, (hipStream_t)stream);
+}
+int kt_dconv_apply(const KtApply* k, void* stream) {
+    DcRewrite rw;
+    rw.w = (const uint16_t*)k->rw_w; rw.kp = (int)k->rw_kp; rw.bias = (const float*)k->rw_bias;
+    rw.out = (uint16_t*)k->rw_out; rw.c4 = (uint16_t*)k->rw_c4;
+    return dconv_apply_launch((const uint16_t*)k->hb, (const uint16_t*)k->w, (int)k->kp, (const float*)k->bias,
+                              (const double*)k->st, (const float*)k->gn_w, (const float*)k->gn_b, (const float*)k->scale,
+                              (uint16_t*)k->x, k->M, k->L, (int)k->C, (hipStream_t)stream, k->rewrite ? &rw : nullptr);
+}
+int kt_dconv_small(const KtDcSmall* k, void* stream) {
+    return dconv_small_launch(k->x, (int)k->x_bf16, (float*)k->h, k->nb, k->L, (int)k->C, (int)k->dil,
+                              (const float*)k->w3, (const float*)k->b3, (const float*)k->g1w, (const float*)k->g1b,
+                              (const float*)k->w1, (const float*)k->b1, (const float*)k->gram1, (const float*)k->g2w,
+                              (const float*)k->g2b, (const float*)k->scale, (double*)k->st_h, (double*)k->st_y,
+                              (hipStream_t)stream, k->fast != 0);
+}
+int kt_gn_gelu_mom(const KtGnMom* k, void* stream) {
+    return gn_gelu_mom_launch((const float*)k->h, (uint16_t*)k->out, (int)k->nb, k->L, (int)k->H, (const double*)k->stats,
+                              (const float*)k->w, (const float*)k->b, (const float*)k->gram, (double*)k->st_y,
+                              (hipStream_t)stream);
+}
+int kt_gn_gelu_bf16in(const uint16_t* h, uint16_t* out, int64_t nb, int64_t per_batch, int64_t H, const double* stats,
+                      const float* w, const float* b, void* stream) {
+    gn_gelu_bf16in_launch(h, out, (int)nb, per_batch, (int)H, stats, w, b, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+int kt_fenc_row(const KtFencRow* k, void* stream) {
+    FencRowDesc d;
+    d.in = k->in; d.a_norm = (const float*)k->a_norm; d.B = (int)k->B; d.Fin = (int)k->Fin; d.Fout = (int)k->Fout;
+    d.T = (int)k->T; d.wc = (const uint16_t*)k->wc; d.wc_ld = (int)k->wc_ld; d.bc = (const float*)k->bc;
+    d.w3_ld = (int)k->w3_ld; d.w1_ld = (int)k->w1_ld;
+    for (int i = 0; i < 2; ++i) {
+        d.w3[i] = (const uint16_t*)k->w3[i]; d.b3[i] = (const float*)k->b3[i];
+        d.g1w[i] = (const float*)k->g1w[i]; d.g1b[i] = (const float*)k->g1b[i];
+        d.w1[i] = (const uint16_t*)k->w1[i]; d.b1[i] = (const float*)k->b1[i];
+        d.g2w[i] = (const float*)k->g2w[i]; d.g2b[i] = (const float*)k->g2b[i];
+        d.gram[i] = (const float*)k->gram[i]; d.scale[i] = (const float*)k->scale[i];
+    }
+    d.wr = (const uint16_t*)k->wr; d.wr_ld = (int)k->wr_ld; d.br = (const float*)k->br;
+    d.row_add = (const float*)k->row_add; d.out = (uint16_t*)k->out; d.out4 = (uint16_t*)k->out4;
+    return fenc_row_launch(d, (int)k->cin, (int)k->c, (hipStream_t)stream);
+}
+int kt_fenc_row_supported(int64_t cin, int64_t c, int64_t T) { return fenc_row_supported((int)cin, (int)c, (int)T); }
+int kt_dconv_conv3_supported(int64_t C, int64_t H, int64_t kp, int64_t L) {
+    return dconv_conv3_supported((int)C, (int)H, (int)kp, L);
+}
+int kt_dconv_apply_supported(int64_t C, int64_t H, int64_t kp, int64_t M) {
+    return dconv_apply_supported((int)C, (int)H, (int)kp, M);
+}
+
+// ---- the host-side packers of ctx.h (no GPU) ----
+int64_t kt_glu_src(int64_t pr, int64_t n) { return athd_ctx::glu_src((int)pr, (int)n); }
+int64_t kt_rewrite_perm(int64_t k) { return dconv_rewrite_perm((int)k); }
+int64_t kt_host_f2bf(int64_t f32_bits) {
+    const uint32_t u = (uint32_t)f32_bits;
+    float f;
+    memcpy(&f, &u, 4);
+    return host_f2bf(f);
+}
+// out: H * H + 2 H + 2 floats
+void kt_conv1x1_moments(const float* w, const float* b, int64_t N, int64_t H, int64_t round_bf16, float* out) {
+    const std::vector<float> g = conv1x1_moments(std::vector<float>(w, w + N * H), std::vector<float>(b, b + N),
+                                                 (int)N, (int)H, round_bf16 != 0);
+    memcpy(out, g.data(), g.size() * sizeof(float));
+}
+
 int kt_gn_apply(float* x, int64_t nb, int64_t N, int64_t C, const double* stats, const float* w, const float* b,
                 void* stream) {
     gn_apply_launch(x, (int)nb, N, (int)C, stats, w, b, (hipStream_t)stream);

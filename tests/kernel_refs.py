@@ -1,4 +1,5 @@
-"""float64 references and derived tolerances for the kernel-level parity tests (tests/test_gpu_kernels.py).
+"""float64 references and derived tolerances for the kernel-level parity tests (tests/test_gpu_kernels.py,
+tests/test_gpu_dconv.py).
 
 Every reference is written from the operation's formula (csrc/gemm.h's header comment, csrc/attn.h, csrc/kernels.h),
 not from a kernel.  Beside every result R it returns tol, an error bound derived from the number formats:
@@ -22,6 +23,60 @@ not from a kernel.  Beside every result R it returns tol, an error bound derived
   |dy_i| <= |w_i| r (d_i + mean(d) + |v_i - m| r rms(d)) + the LayerNorm kernel's own bound (layernorm_ref).
 * Statistics {sum, sumsq} of values R_i known to tol_i:  |dsum| <= sum tol_i, |dsumsq| <= sum (2 |R_i| tol_i + tol_i^2);
   the f32 partial sums of at most a tile of rows add n_part e sum|R_i| (n_part <= 64 additions per lane).
+
+The DConv kernels (tests/test_gpu_dconv.py; formulas: csrc/kernels.h, the header comments of csrc/dconv.hip and
+SURVEY.md Appendix A: conv3 -> GroupNorm(1) -> GELU -> 1x1 -> GroupNorm(1) -> GLU -> LayerScale -> residual) add:
+
+* GLU step a sigma(g) of a, g known to da, dg:  d(a sigma) = sigma da + a sigma' dg with sigma' = sigma (1 - sigma)
+  <= 1/4, so |d| <= |da| sigma(g) + |a| (|dg| / 4 + 4e); the 4e covers the f32 exp, add, divide and product.  The
+  bf16 mode's sigmoid_fast is rcp(1 + exp2(-g log2 e)) on v_exp_f32 and v_rcp_f32 (about 1 ulp = 2e each, common.h):
+  the argument's rounding moves t = exp(-g) by |g| e relative and v_exp by 2e more, d sigma = sigma (1 - sigma) dt / t;
+  the add rounds once (e) and v_rcp adds 2e relative to sigma.  Together |d sigma| <= sigma ((1 - sigma)(|g| + 4) + 4) e,
+  which multiplies |a| (term `fast`).
+* GroupNorm from statistics known to a bound (dm on the mean, drr = dr / r on rstd), values known to d:
+  z = (v - m) r w + b,  |dz| <= |w| r (d + dm + |v - m| drr) + 4e (|c| + |b| + |m| r |w|) with c = (v - m) r w: the
+  LayerNorm rule above with the statistics' own bound as input instead of mean(d), rms(d).  Statistics a kernel reads
+  from memory (fp64 {sum, sumsq} written by an earlier pass) are exact inputs: dm = drr = 0.
+* Moment-form statistics of y = W x + b over its N outputs (ctx.h conv1x1_moments: G = W^T W, v = W^T b, ws = W^T 1):
+  sum_n y = sum b + ws.x,  sum_n y^2 = sum b^2 + 2 v.x + x^T G x.  The reference evaluates y itself in f64 from the
+  row x the kernel stored (bf16, checked separately: no rounding-tie ambiguity).  The kernel evaluates the form in f32:
+  H^2 + H products and as many additions for the quadratic term, 2H for each linear term, 4 to combine, every one
+  bounded by e times the form on absolute values A = (|sum b| + |ws|.|x|,  sum b^2 + 2 |v|.|x| + |x|^T |G| |x|), so
+  (H^2 + 3H + 4) e A; the moments themselves are f32 roundings of f64 sums, e relative per entry: + e A.  Per-position
+  values are added in fp64 over n positions: + n 2^-53 sum A (the term stats_of takes as n64).  Where x is only known
+  to d (dconv_small: x = GELU(GN(stored h))) the form's derivative adds |ws|.d and 2 |v|.d + 2 (|G| |x|).d + d^T |G| d.
+* bf16 rounding of a value known only to d (the updated row before the fused rewrite): bf16_round_amb(a, d) marks an
+  element within d' = 8e |a| + d of a rounding tie; it gets one bf16 ulp, times |W| of the GEMM that reads it.  One
+  ulp holds only while d' <= ulp / 2, and below a power of two the spacing halves, so the function takes the bound
+  from monotonicity instead: the kernel's bf16 lies between bf16(a - d') and bf16(a + d').
+* fenc_row (a whole encoder level per (b, f) row, end to end): both GroupNorm statistics of a layer are one-pass f32
+  sums over the row's n values v (gn_from_sums): s1 = sum v, s2 = sum v^2, m = s1 / n, var = s2 / n - m^2.  With the
+  values known to t:  |ds1| <= sum t + n_part e sum |v|,  |ds2| <= sum (2 |v| t + t^2) + (n_part + 2) e sum v^2, so
+  dm = |ds1| / n + e |m| and dvar = |ds2| / n + 2 |m| dm + dm^2 + 3e (s2 / n + m^2): the variance bound carries
+  n_part e sum v^2 / n however small var is, which is what a large mean-to-deviation ratio amplifies.  drr is the
+  larger relative change of (var + eps)^-1/2 over var +- dvar (var - dvar clamped at 0) + 4e for the add, sqrtf and
+  divide.  n_part is the depth of the documented reduction: level 0 - 12 additions per lane (3 m-tiles x 4
+  channels), 4 DPP row steps, 2 readlane levels, 3 levels over the 8 waves = 21; level 1 - 8 per lane (2 m-tiles),
+  6 wave_sum steps, 12 sequential wave partials = 26.  The 1x1 statistics are the moment form per position added in
+  f32 the same way (level 0: 1 + 4 + 2 + 3 = 10, level 1: 2 + 6 + 12 = 20 additions of partial forms, each bounded
+  by the form on absolute values).  The 1x1 apply uses the folded affine y' wa + ca with wa = r w s, ca = ((b1 - m)
+  r w + beta) s (s the LayerScale; the gate half carries -log2 e instead): y' and b1 - m no longer cancel before the
+  roundings, so 6e (|y'| + |b1 - m|) r |w| + 4e |beta| is added.  The residual stream x stays in f32 (bound d,
+  accumulated over the stages); its bf16 image and the bf16 hidden tile follow bf16_round_amb(., d).
+  The reference's GELU here is the tanh form v sigmoid(u), u = sqrt(8 / pi) (v + 0.044715 v^3), the function the bf16
+  mode documents (common.h gelu_fast), not the erf form + GELU_FAST_ABS: carried as an unknown error, 4.8e-4 puts 70 %
+  of the first bf16 image within the bound of a rounding tie and the end-to-end bound reaches 7e2 at the output.
+  gelu_fast evaluates x rcp(1 + exp2(x fma(K1, x^2, K0))): five roundings in the argument (e |u| each on exp), v_exp
+  and v_rcp about 2e each, the add and the product e each, and |gelu_tanh'| <= 1.13:
+  |d| <= 1.13 t + |v| sigma ((1 - sigma)(5 |u| + 2) + 4) e.
+  Even so the bound is worst case over every tie and every sum |w|: it grows by about 2 (tie) x 11 (sum |w| of conv3)
+  x 2.4 (1x1) x 1.3 per DConv layer.  Level 0 ends with a median bound of 0.4 .. 1.0 on outputs that carry row scales
+  of 1 .. 16, where a float32 evaluation (bf16 flips included) uses 0.01 .. 0.6 of it: it separates wrong taps, rows,
+  embeddings and channels, not a statistics count off by 5 %.  Level 1 (conv K = 384: a bound of 1.8e-4 on the first
+  image, 44 % of it within that of a tie, every element after the first layer) ends at 1e3: the comparison there only
+  shows finite values of the right order.  tests/test_dconv_refs.py holds the measured figures and asserts them.
+* Short GroupNorm rows (L = 1, 2 in dconv_small) have a tiny variance, so rstd is large (up to 316) and every bound
+  above that carries r grows with it.  That is the arithmetic's own conditioning, not slack.
 """
 import math
 from types import SimpleNamespace
@@ -56,16 +111,16 @@ def bf16_round(x):
     return bf16_value(bf16_bits(np.asarray(x, dtype=np.float32))).astype(np.float64)
 
 
-def bf16_round_amb(a64):
-    """bf16(a) for f64 values that a kernel computed in f32 before converting: (rounded, amb) with amb = one bf16 ulp
-    where a lies within 8e |a| of a rounding tie (the kernel may have rounded the other way), else 0."""
+def bf16_round_amb(a64, d=0.0):
+    """bf16(a) for f64 values that a kernel computed in f32 before converting: (rounded, amb).  The kernel's value lies
+    within d' = 8e |a| + d of a (d: absolute bound on it before the conversion, scalar or array) and rounding is
+    monotone, so its bf16 lies between bf16(a - d') and bf16(a + d'): amb is the larger distance of the two from
+    bf16(a).  That is 0 unless a rounding tie lies within d' of a, and then one bf16 ulp (the kernel may have rounded
+    the other way) as long as d' is below half an ulp."""
     a64 = np.asarray(a64, dtype=np.float64)
     r = bf16_round(a64)
-    mant, expo = np.frexp(np.where(a64 == 0, 1.0, a64))
-    ulp = np.ldexp(1.0, expo - 8)                      # bf16: 8 significant bits
-    frac = np.abs(a64 - r) / ulp                       # 0 .. 0.5
-    amb = np.where((0.5 - frac) * ulp <= 8 * E32 * np.abs(a64), ulp, 0.0)
-    return r, np.where(a64 == 0, 0.0, amb)
+    dd = 8 * E32 * np.abs(a64) + d
+    return r, np.maximum(r - bf16_round(a64 - dd), bf16_round(a64 + dd) - r)
 
 
 def hulp16(x):
@@ -207,13 +262,14 @@ def convt_ref(x, wp, bias, res_off=RES_OFF):
     return R, tol_acc + hulp16(np.abs(R) + tol_acc), S, tol_acc
 
 
-def stats_of(R, tol, n_part=64):
-    """{sum, sumsq} of R (any shape, reduced over all axes but the first) and their bounds (module docstring)"""
+def stats_of(R, tol, n_part=64, n64=0):
+    """{sum, sumsq} of R (any shape, reduced over all axes but the first) and their bounds (module docstring); n64:
+    the number of fp64 additions behind one sum (2^-53 relative each)"""
     ax = tuple(range(1, R.ndim))
     a = np.abs(R)
     s1, s2 = R.sum(axis=ax), (R * R).sum(axis=ax)
-    t1 = tol.sum(axis=ax) + n_part * E32 * a.sum(axis=ax)
-    t2 = (2 * a * tol + tol * tol).sum(axis=ax) + (n_part + 2) * E32 * (R * R).sum(axis=ax)
+    t1 = tol.sum(axis=ax) + (n_part * E32 + n64 * 2.0 ** -53) * a.sum(axis=ax)
+    t2 = (2 * a * tol + tol * tol).sum(axis=ax) + ((n_part + 2) * E32 + n64 * 2.0 ** -53) * (R * R).sum(axis=ax)
     return np.stack([s1, s2], axis=-1), np.stack([t1, t2], axis=-1)
 
 
@@ -389,3 +445,353 @@ def gemm_ref(g, mode, tap_shift=0, pad_neighbour=False, stats_shift=False):
             out.c4_idx = ((rows // g.ldo)[:, :, None] * 4 + np.arange(4)).ravel()
             out.c4_R, out.c4_tol = store_R[:, :, :4].ravel(), t[:, :, :4].ravel()
     return out
+
+
+# ------------------------------------------------------------------------------------------------ DConv packers
+def glu_src(pr, n):
+    """ctx.h: packed row pr of a GLU-interleaved [n = 2C] layer reads natural row glu_src: per 32 packed rows
+    [a(16q .. 16q+15) | gate(C + 16q .. C + 16q + 15)]"""
+    C, q, s = n // 2, pr // 32, pr % 32
+    return 16 * q + s if s < 16 else C + 16 * q + (s - 16)
+
+
+def glu_order(v):
+    """a [2C] (or [2C][...]) array in packed GLU order"""
+    v = np.asarray(v)
+    return v[[glu_src(i, v.shape[0]) for i in range(v.shape[0])]]
+
+
+def rewrite_perm(k):
+    """K slot k of the fused rewrite's weights holds channel rewrite_perm(k) (kernels.h DcRewrite, ctx.h
+    dconv_rewrite_perm): slot 32 ks + 8 g + i <- channel 32 ks + 4 g + i (i < 4) or 32 ks + 16 + 4 g + (i - 4)"""
+    ks, g, i = k // 32, (k % 32) // 8, k % 8
+    return 32 * ks + (4 * g + i if i < 4 else 16 + 4 * g + (i - 4))
+
+
+def conv3_pack(w3, rows=None):
+    """Conv1d weight [H][C][3] -> [rows][tap * C + c] (rows >= H, the extra ones zero: the MFMA tile of 16)"""
+    H, C, _ = w3.shape
+    out = np.zeros((rows or H, 3 * C), dtype=np.float64)
+    out[:H] = np.transpose(w3, (0, 2, 1)).reshape(H, 3 * C)
+    return out
+
+
+def conv1x1_pack(w1, kp=64):
+    """1x1 weight [2C][H] -> GLU-interleaved rows, K zero-padded to kp"""
+    out = np.zeros((w1.shape[0], kp), dtype=np.float64)
+    out[:, :w1.shape[1]] = glu_order(w1)
+    return out
+
+
+def rewrite_pack(wr):
+    """rewrite weight [2C][C] -> GLU-interleaved rows in the K order of rewrite_perm, K = roundup(C, 32)"""
+    n, C = wr.shape
+    K2 = (C + 31) // 32 * 32
+    src = glu_order(wr)
+    out = np.zeros((n, K2), dtype=np.float64)
+    for k in range(K2):
+        ch = rewrite_perm(k)
+        if ch < C:
+            out[:, k] = src[:, ch]
+    return out
+
+
+def conv1x1_moments(w, b, round_bf16):
+    """[G = W^T W (H x H) | v = W^T b | ws = W^T 1 | sum b | sum b^2] of W [N][H], b [N] as float32, accumulated in
+    float64 row by row (ctx.h conv1x1_moments); round_bf16: from the bf16-rounded weights"""
+    w = np.asarray(w, dtype=np.float32)
+    w = bf16_round(w) if round_bf16 else w.astype(np.float64)
+    b = np.asarray(b, dtype=np.float32).astype(np.float64)
+    N, H = w.shape
+    G, v, ws, sb, sb2 = np.zeros((H, H)), np.zeros(H), np.zeros(H), 0.0, 0.0
+    for n in range(N):
+        G += np.outer(w[n], w[n])
+        v += b[n] * w[n]
+        ws += w[n]
+        sb += b[n]
+        sb2 += b[n] * b[n]
+    return np.concatenate([G.ravel(), v, ws, [sb, sb2]]).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------ DConv references
+def group_sums(v, L):
+    """{sum, sumsq} per GroupNorm row of v [M][n] (rows of L positions, the last one possibly short)"""
+    M = v.shape[0]
+    gi = np.arange(M) // L
+    ng = int(gi[-1]) + 1
+    return np.stack([np.bincount(gi, v.sum(1), ng), np.bincount(gi, (v * v).sum(1), ng)], -1)
+
+
+def dconv_conv3_ref(x, w3, bias, dil, mut=None):
+    """h[b][t][j] = bias[j] + sum_{tap, c} w3[j][c][tap] x[b][t + (tap - 1) dil][c], zero outside [0, L).
+    x [nb][L][C] (values exact in the compute type), w3 [H][C][3].  tol = (3C + 16) e S (GEMM rule), batch by batch
+    (large cases).  mut: 'neighbour' (a tap past a row end reads the neighbouring row), 'reversed' (taps reversed)."""
+    nb, L, C = x.shape
+    H = w3.shape[0]
+    R, S = np.empty((nb, L, H)), np.empty((nb, L, H))
+    flat = x.reshape(nb * L, C)
+    for b in range(nb):
+        r = np.tile(np.asarray(bias, dtype=np.float64), (L, 1))
+        s = np.abs(r)
+        for tap in range(3):
+            off = (tap - 1) * dil
+            xs = np.zeros((L, C))
+            if mut == "neighbour":
+                p = b * L + np.arange(L) + off
+                ok = (p >= 0) & (p < nb * L)
+                xs[ok] = flat[p[ok]]
+            else:
+                t0, t1 = max(0, -off), min(L, L - off)
+                if t1 > t0:
+                    xs[t0:t1] = x[b, t0 + off:t1 + off]
+            wt = w3[:, :, 2 - tap if mut == "reversed" else tap]
+            r += xs @ wt.T
+            s += np.abs(xs) @ np.abs(wt).T
+        R[b], S[b] = r, s
+    return R, (3 * C + 16) * E32 * S
+
+
+def conv3_stats_ref(h, L, n_part=16, mut=None):
+    """{sum, sumsq} per row of the stored h [nb * L][H] (exact inputs).  The kernels add at most 12 values per lane in
+    f32 (H / TPP outputs of a position, or 4 NT of a 16-row unit's lane) before going to fp64: n_part = 16; the fp64
+    sums run over L H values.  mut 'unit_first': every 16-row unit's sums credited to the row of its first position."""
+    M, H = h.shape
+    st, tol = stats_of(h.reshape(-1, L, H), np.zeros((M // L, L, H)), n_part=n_part, n64=L * H)
+    if mut == "unit_first":
+        gi = (np.arange(M) // 16 * 16) // L
+        ng = M // L
+        st = np.stack([np.bincount(gi, h.sum(1), ng), np.bincount(gi, (h * h).sum(1), ng)], -1)
+    return st, tol
+
+
+def gn_affine(v, gi, stats, count, w, b, d=0.0, dm=0.0, drr=0.0):
+    """z = (v - m) r w + b with (m, r) of GroupNorm row gi[p] for position p (v [M][n]); the rule of the module
+    docstring.  Returns (z, tol)."""
+    m, r = gn_params(stats, count)
+    m, r = m[gi][:, None], r[gi][:, None]
+    c = (v - m) * r * w
+    tol = np.abs(w) * r * (d + dm + np.abs(v - m) * drr) + 4 * E32 * (np.abs(c) + np.abs(b) + np.abs(m) * r * np.abs(w))
+    return c + b, tol
+
+
+def gelu_step(v, tol, fast):
+    """the parent's GELU rule: 1.13 x the input bound + 8e |v| (+ GELU_FAST_ABS for the tanh form)"""
+    return gelu(v), 1.13 * tol + 8 * E32 * np.abs(v) + (GELU_FAST_ABS if fast else 0.0)
+
+
+def gelu_tanh(v):
+    """the bf16 mode's GELU as common.h documents it: v sigmoid(sqrt(8 / pi) (v + 0.044715 v^3))"""
+    with np.errstate(over="ignore"):
+        return v * sigmoid(1.5957691216057308 * (v + 0.044715 * v ** 3))
+
+
+def gelu_tanh_step(v, tol):
+    """gelu_tanh(v) of v known to tol, evaluated as gelu_fast does (module docstring, fenc_row)"""
+    u = 1.5957691216057308 * (v + 0.044715 * v ** 3)
+    with np.errstate(over="ignore"):               # (exp(-u) -> inf for very negative v: sigmoid 0)
+        sg = sigmoid(u)
+    return v * sg, 1.13 * tol + np.abs(v) * sg * ((1.0 - sg) * (5.0 * np.abs(u) + 2.0) + 4.0) * E32
+
+
+def glu_step(a, da, g, dg, fast):
+    """a sigma(g) and its bound (module docstring)"""
+    sg = sigmoid(g)
+    f = sg * ((1.0 - sg) * (np.abs(g) + 4.0) + 4.0) * E32 if fast else 0.0
+    return a * sg, da * sg + np.abs(a) * (dg / 4 + 4 * E32 + f)
+
+
+def gn_gelu_ref(h, L, stats, w, b, fast=True, out_bf16=True):
+    """GELU(GN(h)) of h [M][H] with the given per-row statistics {sum, sumsq} over L H values -> (y, tol)"""
+    M, H = h.shape
+    z, tz = gn_affine(h, np.arange(M) // L, stats, L * H, w, b)
+    y, t = gelu_step(z, tz, fast)
+    if out_bf16:
+        t = t + hulp16(np.abs(y) + t)
+    return y, t
+
+
+def moment_stats_ref(x, L, w1, b1, d=None, mut=None, chunk=1 << 15, n_part=0):
+    """GroupNorm statistics {sum, sumsq} of y = W1 x + b1 (N = 2C outputs) per row of L positions, x [M][H], and
+    the bound of their moment-form evaluation in f32 (module docstring); evaluated chunk positions at a time.
+    d: bound on x (None: exact).
+    mut: 'swap' (v and ws swapped), 'no2' (factor 2 dropped), 'nob2' (sum b^2 dropped), 'boundary' (the first
+    position of every row but the first credited to the row before)."""
+    M, H = x.shape
+    G, v, ws, sb, sb2 = w1.T @ w1, w1.T @ b1, w1.sum(0), b1.sum(), (b1 * b1).sum()
+    aG = np.abs(G)
+    k = (H * H + 3 * H + 4 + 1 + n_part) * E32      # n_part: f32 additions between positions (fenc_row)
+    n64 = L * 2.0 ** -53
+    ng = (M + L - 1) // L
+    st, tol = np.zeros((ng, 2)), np.zeros((ng, 2))
+    for p0 in range(0, M, chunk):
+        xc = x[p0:p0 + chunk]
+        y = xc @ w1.T + b1
+        s1, s2 = y.sum(1), (y * y).sum(1)
+        if mut == "swap":
+            s1, s2 = sb + xc @ v, sb2 + 2 * (xc @ ws) + ((xc @ G) * xc).sum(1)
+        elif mut == "no2":
+            s2 = sb2 + xc @ v + ((xc @ G) * xc).sum(1)
+        elif mut == "nob2":
+            s2 = s2 - sb2
+        ax = np.abs(xc)
+        A1 = abs(sb) + ax @ np.abs(ws)
+        A2 = sb2 + 2 * (ax @ np.abs(v)) + ((ax @ aG) * ax).sum(1)
+        t1, t2 = k * A1, k * A2
+        if d is not None:
+            dc = d[p0:p0 + chunk]
+            t1 = t1 + dc @ np.abs(ws)
+            t2 = t2 + 2 * (dc @ np.abs(v)) + 2 * ((ax @ aG) * dc).sum(1) + ((dc @ aG) * dc).sum(1)
+        pos = np.arange(p0, p0 + xc.shape[0])
+        gi0 = pos // L
+        gi = gi0
+        if mut == "boundary":
+            gi = gi0 - ((pos % L == 0) & (gi0 > 0))
+        st += np.stack([np.bincount(gi, s1, ng), np.bincount(gi, s2, ng)], -1)
+        tol += np.stack([np.bincount(gi0, t1 + n64 * A1, ng), np.bincount(gi0, t2 + n64 * A2, ng)], -1)
+    return st, tol
+
+
+def dconv_apply_ref(hv, d_hv, w1, b1, st_y, L, g2w, g2b, scale, x, fast, out_bf16, mut=None, dm=0.0, drr=0.0,
+                    folded=False):
+    """x + scale GLU(GN(W1 hv + b1)) per position: hv [M][H] known to d_hv (None: exact), w1 [2C][H], b1 / g2w / g2b
+    [2C] in natural order ('a' half first), st_y the given per-row {sum, sumsq} of the 1x1 output over L 2C values,
+    scale [C], x [M][C].  Returns (R, tol_value, tol_stored): the bound of the f32 value and of what is stored (bf16:
+    + half an ulp).  1x1: (H + 16) e S + |W1| d_hv; GroupNorm, GLU rules; LayerScale and residual: |scale| d +
+    2e (|x| + |scale glu|).
+    mut: 'swap' (a and gate halves swapped), 'gate_tile' (gate from the neighbouring 16-channel tile), 'scale_packed'
+    (LayerScale indexed by the packed column), 'unit_first' (GroupNorm row of the 16-row unit's first position),
+    'no_res' (residual not added).  dm, drr: the bound of the statistics themselves (0: read from memory); folded:
+    the affine in fenc_row's folded form."""
+    M, H = hv.shape
+    C = w1.shape[0] // 2
+    y = hv @ w1.T + b1
+    S = np.abs(hv) @ np.abs(w1).T + np.abs(b1)
+    ty = (H + 16) * E32 * S
+    if d_hv is not None:
+        ty = ty + d_hv @ np.abs(w1).T
+    gi = np.arange(M) // L
+    if mut == "unit_first":
+        gi = (np.arange(M) // 16 * 16) // L
+    z, tz = gn_affine(y, gi, st_y, L * 2 * C, g2w, g2b, d=ty, dm=dm, drr=drr)
+    if folded:      # fenc_row: y' (r w s) + ((b1 - m) (r w) + beta) s, see the module docstring
+        m_, r_ = gn_params(st_y, L * 2 * C)
+        m_, r_ = m_[gi][:, None], r_[gi][:, None]
+        tz = tz + 6 * E32 * (np.abs(y - b1) + np.abs(b1 - m_)) * r_ * np.abs(g2w) + 4 * E32 * np.abs(g2b)
+    a, g, ta, tg = z[:, :C], z[:, C:], tz[:, :C], tz[:, C:]
+    if mut == "swap":
+        a, g, ta, tg = g, a, tg, ta
+    if mut == "gate_tile":
+        perm = (np.arange(C) + 16) % C
+        g, tg = g[:, perm], tg[:, perm]
+    glu, tglu = glu_step(a, ta, g, tg, fast)
+    sc = np.asarray(scale, dtype=np.float64)
+    if mut == "scale_packed":      # channel c sits at packed column 32 (c // 16) + c % 16
+        sc = sc[(32 * (np.arange(C) // 16) + np.arange(C) % 16) % C]
+    res = 0.0 if mut == "no_res" else x
+    R = res + sc * glu
+    tol = np.abs(sc) * tglu + 2 * E32 * (np.abs(x) + np.abs(sc * glu))
+    return R, tol, tol + (hulp16(np.abs(R) + tol) if out_bf16 else 0.0)
+
+
+def dconv_rewrite_ref(xnew, d, wr, br, mut=None, row_add=None):
+    """The encoder layer's rewrite on the updated rows: GLU(Wr bf16(xnew) + br), wr [2C][C] natural order, xnew known
+    to d before its bf16 rounding.  tol = (C + 16) e S + amb |Wr| through the GLU rule + half a bf16 ulp.
+    mut 'natural_k': the kernel's K slots read in natural instead of permuted order."""
+    C = xnew.shape[1]
+    xb, amb = bf16_round_amb(xnew, d)
+    if mut == "natural_k":
+        K2 = (C + 31) // 32 * 32
+        wp = rewrite_pack(wr)                       # [2C][K2] packed rows
+        xk = np.zeros((xnew.shape[0], K2))
+        xk[:, :C] = xb                              # slot k <- channel k
+        inv = [glu_src(i, 2 * C) for i in range(2 * C)]
+        y = np.empty((xnew.shape[0], 2 * C))
+        y[:, inv] = xk @ wp.T
+        y = y + br
+    else:
+        y = xb @ wr.T + br
+    S = np.abs(xb) @ np.abs(wr).T + np.abs(br)
+    ty = (C + 16) * E32 * S + amb @ np.abs(wr).T
+    if row_add is not None:       # fenc_row level 0 (gate bias and scaling folded: two more roundings of the gate)
+        ty = ty + 4 * E32 * S
+    out, t = glu_step(y[:, :C], ty[:, :C], y[:, C:], ty[:, C:], True)
+    if row_add is not None:
+        out = out + row_add
+        t = t + 2 * E32 * (np.abs(out) + np.abs(row_add))
+    return out, t + hulp16(np.abs(out) + t)
+
+
+# ------------------------------------------------------------------------------------------------ fenc_row
+FENC_NPART = {0: (21, 10), 1: (26, 20)}       # f32 reduction depth of the (conv3, 1x1) statistics (module docstring)
+
+
+def onepass_bounds(v, t, n_part, count=None):
+    """one-pass f32 GroupNorm statistics of the values v known to t (module docstring) -> ({sum, sumsq}, dm, drr)"""
+    n = v.size if count is None else count
+    s1, s2 = v.sum(), (v * v).sum()
+    a = np.abs(v)
+    return _onepass(s1, s2, t.sum() + n_part * E32 * a.sum(),
+                    (2 * a * t + t * t).sum() + (n_part + 2) * E32 * s2, n)
+
+
+def _onepass(s1, s2, ds1, ds2, n):
+    m = s1 / n
+    dm = ds1 / n + E32 * abs(m)
+    var = max(s2 / n - m * m, 0.0)
+    dvar = ds2 / n + 2 * abs(m) * dm + dm * dm + 3 * E32 * (s2 / n + m * m)
+    r = 1.0 / math.sqrt(var + 1e-5)
+    lo, hi = 1.0 / math.sqrt(var + dvar + 1e-5), 1.0 / math.sqrt(max(var - dvar, 0.0) + 1e-5)
+    return np.array([[s1, s2]]), dm, max(1.0 - lo / r, hi / r - 1.0) + 4 * E32
+
+
+def fenc_row_ref(level, p, xin, a_norm, f, Fin, row_add=None, mut=None):
+    """One (b, f) row of a frequency-encoder level (fenc_row.hip's header): Conv2d (8,1) stride
+    (4,1) padding (2,0) over frequency -> GELU -> two DConv layers (dilation 1, 2) over the row's T positions ->
+    rewrite 1x1 -> GLU (+ the frequency embedding row).  xin: the batch item's input as [Fin][T][Cin] values (level 0:
+    raw f32 values, normalised here by a_norm = (sub, div) and rounded to bf16; level 1: bf16 values).  p: natural-
+    order weights (wc [C][Cin][8], bc, and per layer w3 [H][C][3], b3, g1w, g1b, w1 [2C][H], b1, g2w, g2b, scale;
+    wr [2C][C], br).  Both GELUs are the tanh form.  Returns (out [T][C], tol) with the end-to-end bound of the module
+    docstring.
+    mut: 'tap_shift' (frequency taps shifted by one), 'emb_next' (embedding row f + 1), 'count_pad' (the statistics
+    count includes the positions of the last 16-position tile >= T)."""
+    T, Cin = xin.shape[1], xin.shape[2]
+    C = p["wc"].shape[0]
+    H = C // 8
+    np3, npy = FENC_NPART[level]
+    a = np.zeros((T, 8, Cin))
+    amb = np.zeros((T, 8, Cin))
+    for tap in range(8):
+        fi = 4 * f - 2 + tap + (1 if mut == "tap_shift" else 0)
+        if 0 <= fi < Fin:
+            if level == 0:
+                a[:, tap], amb[:, tap] = bf16_round_amb((xin[fi] - a_norm[0]) / a_norm[1])
+            else:
+                a[:, tap] = xin[fi]
+    wc = np.transpose(p["wc"], (0, 2, 1)).reshape(C, 8 * Cin)          # [C][tap Cin + ci]
+    a, amb = a.reshape(T, 8 * Cin), amb.reshape(T, 8 * Cin)
+    v = a @ wc.T + p["bc"]
+    tv = (8 * Cin + 16) * E32 * (np.abs(a) @ np.abs(wc).T + np.abs(p["bc"])) + amb @ np.abs(wc).T
+    x, d = gelu_tanh_step(v, tv)
+    Tc = (T + 15) // 16 * 16 if mut == "count_pad" else T
+    for dd in range(2):
+        q = p["dc"][dd]
+        xb, ax = bf16_round_amb(x, d)
+        h, th = dconv_conv3_ref(xb[None], q["w3"], q["b3"], 1 << dd)
+        th = th[0] + dconv_conv3_ref(ax[None], np.abs(q["w3"]), np.zeros(H), 1 << dd)[0][0]
+        h = h[0]
+        st, dm, drr = onepass_bounds(h, th, np3, count=H * Tc)
+        z, tz = gn_affine(h, np.zeros(T, dtype=np.int64), st, H * Tc, q["g1w"], q["g1b"], d=th, dm=dm, drr=drr)
+        hv, dhv = gelu_tanh_step(z, tz)
+        hb, ah = bf16_round_amb(hv, dhv)
+        sy, sty = moment_stats_ref(hb, T, q["w1"], q["b1"], d=ah, n_part=npy)
+        _, dmy, drry = _onepass(sy[0, 0], sy[0, 1], sty[0, 0], sty[0, 1], 2 * C * Tc)
+        # (count_pad: sums over T positions divided by 2C Tc, i.e. the statistics scaled by T / Tc)
+        xn, t, _ = dconv_apply_ref(hb, ah, q["w1"], q["b1"], sy * (T / Tc), T, q["g2w"], q["g2b"], q["scale"], x, True,
+                                   False, dm=dmy, drr=drry, folded=True)
+        x, d = xn, d + t
+    ra = None
+    if row_add is not None:
+        ra = row_add[(f + 1) % row_add.shape[0] if mut == "emb_next" else f]
+    elif level == 0:
+        ra = np.zeros(C)
+    return dconv_rewrite_ref(x, d, p["wr"], p["br"], row_add=ra)

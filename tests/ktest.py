@@ -1,5 +1,6 @@
 """ctypes binding of libathd_ktest.so (csrc/ktest.cpp): the kernel launchers of libathd.so behind flat descriptors.
-A plain helper module of tests/test_gpu_kernels.py; importing it needs the built libraries but no GPU."""
+A plain helper module of tests/test_gpu_kernels.py and tests/test_gpu_dconv.py; importing it needs the built libraries
+but no GPU (the host-side packers it exports are compared on the CPU, tests/test_dconv_refs.py)."""
 import ctypes
 import json
 import os
@@ -31,13 +32,26 @@ ATTN_FIELDS = ("Q q_bf16 q_bs q_ld q_off K k_bf16 k_bs k_ld k_off V v_bf16 v_bs 
                "nb Nq Nk heads scale_bits").split()
 LN_FIELDS = "x nb N C w b gn_stats gn_w gn_b gn_writeback pos out out_bf16 w2 b2 out2".split()
 CT_FIELDS = "x w bias out stats nb H W keep".split()
+C3_FIELDS = "x w kp bias h st M L C dil".split()
+AP_FIELDS = "hb w kp bias st gn_w gn_b scale x M L C rewrite rw_w rw_kp rw_bias rw_out rw_c4".split()
+DS_FIELDS = "x x_bf16 h nb L C dil w3 b3 g1w g1b w1 b1 gram1 g2w g2b scale st_h st_y fast".split()
+GM_FIELDS = "h out nb L H stats w b gram st_y".split()
+# (the [2] pointer arrays of FencRowDesc as two fields each: name0, name1)
+FR_FIELDS = ("in_ a_norm B Fin Fout T wc wc_ld bc w30 w31 w3_ld b30 b31 g1w0 g1w1 g1b0 g1b1 w10 w11 w1_ld b10 b11 "
+             "g2w0 g2w1 g2b0 g2b1 gram0 gram1 scale0 scale1 wr wr_ld br row_add out out4 cin c").split()
 
 KtGemm = _struct("KtGemm", GEMM_FIELDS, GEMM_PTRS)
 KtAttn = _struct("KtAttn", ATTN_FIELDS, {"Q", "K", "V", "O"})
 KtLn = _struct("KtLn", LN_FIELDS, set("x w b gn_stats gn_w gn_b pos out w2 b2 out2".split()))
 KtConvT4 = _struct("KtConvT4", CT_FIELDS, set("x w bias out stats".split()))
+KtConv3 = _struct("KtConv3", C3_FIELDS, set("x w bias h st".split()))
+KtApply = _struct("KtApply", AP_FIELDS, set("hb w bias st gn_w gn_b scale x rw_w rw_bias rw_out rw_c4".split()))
+KtDcSmall = _struct("KtDcSmall", DS_FIELDS, set("x h w3 b3 g1w g1b w1 b1 gram1 g2w g2b scale st_h st_y".split()))
+KtGnMom = _struct("KtGnMom", GM_FIELDS, set("h out stats w b gram st_y".split()))
+KtFencRow = _struct("KtFencRow", FR_FIELDS, set(FR_FIELDS) - set("B Fin Fout T wc_ld w3_ld w1_ld wr_ld cin c".split()))
 
-for _n in ("gemm", "attn", "ln", "convt4"):
+_NEW = (("conv3", KtConv3), ("apply", KtApply), ("dcsmall", KtDcSmall), ("gnmom", KtGnMom), ("fencrow", KtFencRow))
+for _n in ("gemm", "attn", "ln", "convt4") + tuple(n for n, _ in _NEW):
     getattr(lib, "kt_sizeof_" + _n).restype = ctypes.c_int64
 lib.kt_sk_bytes.restype = ctypes.c_int64
 lib.kt_sk_resident.restype = ctypes.c_int64
@@ -56,11 +70,34 @@ lib.kt_input_norm_params.argtypes = [_P, _I, _I, _P, _P, _P]
 lib.kt_gn_gelu.argtypes = [_P, _I, _I, _I, _P, _P, _P, _I, _P]
 lib.kt_gn_gelu_bf16.argtypes = [_P, _P, _I, _I, _I, _P, _P, _P, _P]
 lib.kt_gn_apply.argtypes = [_P, _I, _I, _I, _P, _P, _P, _P]
+for _n in ("dconv_conv3", "dconv_apply", "dconv_small", "gn_gelu_mom", "fenc_row"):
+    getattr(lib, "kt_" + _n).argtypes = [_P, _P]
+lib.kt_gn_gelu_bf16in.argtypes = [_P, _P, _I, _I, _I, _P, _P, _P, _P]
+lib.kt_fenc_row_supported.argtypes = [_I, _I, _I]
+lib.kt_dconv_conv3_supported.argtypes = [_I, _I, _I, _I]
+lib.kt_dconv_apply_supported.argtypes = [_I, _I, _I, _I]
+for _n in ("glu_src", "rewrite_perm", "host_f2bf"):
+    getattr(lib, "kt_" + _n).restype = _I
+lib.kt_glu_src.argtypes = [_I, _I]
+lib.kt_rewrite_perm.argtypes = [_I]
+lib.kt_host_f2bf.argtypes = [_I]
+lib.kt_conv1x1_moments.restype = None
+lib.kt_conv1x1_moments.argtypes = [_P, _P, _I, _I, _I, _P]
+
+
+def conv1x1_moments(w, b, round_bf16):
+    """ctx.h conv1x1_moments of W [N][H], b [N] -> float32 [H*H + 2H + 2]"""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    N, H = w.shape
+    out = np.zeros(H * H + 2 * H + 2, dtype=np.float32)
+    lib.kt_conv1x1_moments(w.ctypes.data, b.ctypes.data, N, H, int(round_bf16), out.ctypes.data)
+    return out
 
 
 def sizes_match():
     return {n: (getattr(lib, "kt_sizeof_" + n)(), ctypes.sizeof(s))
-            for n, s in (("gemm", KtGemm), ("attn", KtAttn), ("ln", KtLn), ("convt4", KtConvT4))}
+            for n, s in (("gemm", KtGemm), ("attn", KtAttn), ("ln", KtLn), ("convt4", KtConvT4)) + _NEW}
 
 
 GEMM_DEFAULTS = dict(nb=1, H_in=1, W=1, a_cs=1, a_bs=-1, a_hs=-1, ntaps=1, in_stride=1, dil=1, H_out=1, H_out_total=1,
@@ -124,22 +161,32 @@ class Buf:
 
 
 def sync():
+    """wait for the device; a HIP error here (a fault in a kernel under test) ends the whole session, so that no
+    further kernel is launched on a device that has faulted"""
     import torch
-    torch.cuda.synchronize()
+    try:
+        torch.cuda.synchronize()
+    except RuntimeError as e:
+        import pytest
+        pytest.exit("HIP error at synchronize; no further kernels are launched: %s" % e, returncode=3)
 
 
 # ---- the parity report ----
 # written to $ATHD_OUT (the measurement scripts' output directory, default bench_out/ in the repository root)
 REPORT = os.path.join(os.environ.get("ATHD_OUT") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                                  "bench_out"), "kernel_parity_report.json")
-_report = {}
+DCONV_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_dconv_report.json")
+_reports = {}
 
 
-def record(case, **kw):
-    _report[case] = kw
+def record(case, report=None, **kw):
+    """report: the file this case belongs to (default REPORT); each file holds the cases recorded into it"""
+    report = report or REPORT
+    rep = _reports.setdefault(report, {})
+    rep[case] = kw
     try:
-        os.makedirs(os.path.dirname(REPORT), exist_ok=True)
-        with open(REPORT, "w") as f:
-            json.dump(_report, f, indent=1, sort_keys=True)
+        os.makedirs(os.path.dirname(report), exist_ok=True)
+        with open(report, "w") as f:
+            json.dump(rep, f, indent=1, sort_keys=True)
     except OSError:
         pass

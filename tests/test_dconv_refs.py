@@ -1,0 +1,488 @@
+"""CPU checks of the DConv part of tests/kernel_refs.py (the references of tests/test_gpu_dconv.py): the Python packers
+equal the product's exported packers bit for bit, the references agree with torch.nn.functional in float64, an honest
+low-precision emulation (numpy float32 on the packed weights, bf16 at the documented rounding points) stays inside
+every tolerance, and every deliberate mutation lands more than 10x outside it."""
+import numpy as np
+import pytest
+
+import kernel_refs as kr
+import test_gpu_dconv as td
+
+f32 = np.float32
+
+
+def _exceeds(R, Rm, tol, factor=10.0):
+    return bool((np.abs(Rm - R) > factor * tol).any())
+
+
+@pytest.fixture(scope="module")
+def kt():
+    import ktest          # (needs the built libraries, no GPU)
+    return ktest
+
+
+# ------------------------------------------------------------------------------------------------ packers
+def test_sizes_match(kt):
+    for name, (a, b) in kt.sizes_match().items():
+        assert a == b, (name, a, b)
+
+
+@pytest.mark.parametrize("n", [96, 192, 384, 768])
+def test_glu_src_equals_product_and_is_permutation(kt, n):
+    src = [kr.glu_src(i, n) for i in range(n)]
+    assert src == [kt.lib.kt_glu_src(i, n) for i in range(n)]
+    assert sorted(src) == list(range(n))
+    # per 32 packed rows: 16 'a' rows, then the 16 gates of the same channels
+    for pr in range(n):
+        q, s = divmod(pr, 32)
+        assert src[pr] == (16 * q + s if s < 16 else n // 2 + 16 * q + s - 16)
+
+
+@pytest.mark.parametrize("C", [48, 96])
+def test_rewrite_perm_equals_product_and_is_bijection(kt, C):
+    K2 = (C + 31) // 32 * 32
+    perm = [kr.rewrite_perm(k) for k in range(K2)]
+    assert perm == [kt.lib.kt_rewrite_perm(k) for k in range(K2)]
+    assert sorted(perm) == list(range(K2))                      # a bijection on the slots, so on the channels < C
+    wr = np.arange(2 * C * C, dtype=np.float64).reshape(2 * C, C) + 1.0
+    wp = kr.rewrite_pack(wr)
+    assert wp.shape == (2 * C, K2)
+    for k in range(K2):
+        if perm[k] < C:
+            assert np.array_equal(wp[:, k], kr.glu_order(wr)[:, perm[k]])
+        else:
+            assert (wp[:, k] == 0).all()
+    assert sorted(p for p in perm if p < C) == list(range(C))
+
+
+def test_host_f2bf_equals_bf16_bits(kt):
+    rng = np.random.default_rng(0)
+    x = np.concatenate([rng.standard_normal(4096).astype(f32) * f32(2.0) ** rng.integers(-20, 20, 4096).astype(f32),
+                        np.array([0x3F808000, 0x3F818000, 0x3F808001, 0x3F807FFF, 0x00008000, 0x80000000, 0],
+                                 dtype=np.uint32).view(f32)])
+    got = [kt.lib.kt_host_f2bf(int(b)) for b in x.view(np.uint32)]
+    assert got == [int(b) for b in kr.bf16_bits(x)]
+
+
+@pytest.mark.parametrize("round_bf16", [0, 1])
+@pytest.mark.parametrize("H", [6, 12, 24, 48])
+def test_moments_equal_product(kt, H, round_bf16):
+    rng = np.random.default_rng(H)
+    w = rng.standard_normal((16 * H, H)).astype(f32)
+    b = rng.standard_normal(16 * H).astype(f32)
+    mine, theirs = kr.conv1x1_moments(w, b, round_bf16), kt.conv1x1_moments(w, b, round_bf16)
+    assert mine.dtype == theirs.dtype and np.array_equal(mine.view(np.uint32), theirs.view(np.uint32))
+    w64 = kr.bf16_round(w) if round_bf16 else w.astype(np.float64)
+    G = mine[:H * H].reshape(H, H)
+    assert np.allclose(G, w64.T @ w64, rtol=1e-6) and np.allclose(mine[H * H:H * H + H], w64.T @ b, rtol=1e-5, atol=1e-6)
+
+
+def test_predicates(kt):
+    L = kt.lib
+    assert [L.kt_fenc_row_supported(4, 48, T) for T in (1, 272, 273)] == [1, 1, 0]
+    assert L.kt_fenc_row_supported(48, 96, 259) == 1 and L.kt_fenc_row_supported(4, 96, 259) == 0
+    assert [L.kt_dconv_conv3_supported(C, C // 8, 3 * C, 16) for C in (48, 64, 96, 192, 384)] == [1, 0, 1, 1, 1]
+    assert L.kt_dconv_conv3_supported(48, 6, 143, 16) == 0 and L.kt_dconv_conv3_supported(48, 6, 144, 15) == 0
+    assert [L.kt_dconv_apply_supported(C, C // 8, 64, 1) for C in (48, 64, 96, 192, 384)] == [1, 0, 1, 1, 1]
+    assert L.kt_dconv_apply_supported(48, 6, 128, 1) == 0 and L.kt_dconv_apply_supported(48, 6, 64, 0) == 0
+
+
+# ------------------------------------------------------------------------------------------------ vs torch.nn.functional
+def _t(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+
+
+def _close(a, b):
+    return float(np.abs(a - b).max()) <= 1e-12 * max(1.0, float(np.abs(b).max()))
+
+
+def _layer(C, nb, L, seed):
+    rng = np.random.default_rng(seed)
+    p = td._small_weights(C, seed)
+    x = (rng.standard_normal((nb, L, C)) + 0.25) * td._rowscale(nb)[:, None, None]
+    return p, x
+
+
+@pytest.mark.parametrize("dil", [1, 2])
+@pytest.mark.parametrize("nb,L", [(3, 1), (2, 2), (3, 17), (2, 64)])
+@pytest.mark.parametrize("C", [48, 96])
+def test_references_equal_functional(C, nb, L, dil):
+    """the whole DConv layer of SURVEY.md Appendix A, stage by stage: conv1d(k3, dilation, padding = dilation) ->
+    group_norm(1) -> gelu (erf) -> conv1d(k1) -> group_norm(1) -> glu -> LayerScale -> residual, then the rewrite"""
+    import torch
+    import torch.nn.functional as F
+    H = C // 8
+    p, x = _layer(C, nb, L, 10 * C + L + dil)
+    xt = _t(x).transpose(1, 2)                                            # [nb][C][L]
+    h_t = F.conv1d(xt, _t(p["w3"]), _t(p["b3"]), padding=dil, dilation=dil)
+    R, _ = kr.dconv_conv3_ref(x, p["w3"], p["b3"], dil)
+    assert _close(R, h_t.transpose(1, 2).numpy())
+    # the packed layout [H][tap C + c] (rows padded to 16) evaluates to the same
+    wp = kr.conv3_pack(p["w3"], 16)
+    xp = np.zeros((nb, L + 4, C))
+    xp[:, 2:2 + L] = x
+    a = np.concatenate([xp[:, 2 + (t - 1) * dil:2 + (t - 1) * dil + L] for t in range(3)], -1)
+    hp = a @ wp.T
+    assert _close(hp[..., :H] + p["b3"], R) and (hp[..., H:] == 0).all()
+    h = R.reshape(nb * L, H)
+    st_h = kr.group_sums(h, L)
+    assert _close(st_h, np.stack([R.reshape(nb, -1).sum(1), (R ** 2).reshape(nb, -1).sum(1)], -1))
+    hv_t = F.gelu(F.group_norm(h_t, 1, _t(p["g1w"]), _t(p["g1b"]), eps=1e-5))
+    hv, _ = kr.gn_gelu_ref(h, L, st_h, p["g1w"], p["g1b"], fast=False, out_bf16=False)
+    assert _close(hv, hv_t.transpose(1, 2).reshape(nb * L, H).numpy())
+    y_t = F.conv1d(hv_t, _t(p["w1"])[:, :, None], _t(p["b1"]))
+    st_y, _ = kr.moment_stats_ref(hv, L, p["w1"], p["b1"])
+    yn = y_t.numpy()
+    assert _close(st_y, np.stack([yn.reshape(nb, -1).sum(1), (yn ** 2).reshape(nb, -1).sum(1)], -1))
+    z_t = F.glu(F.group_norm(y_t, 1, _t(p["g2w"]), _t(p["g2b"]), eps=1e-5), dim=1)
+    xn_t = xt + _t(p["scale"])[None, :, None] * z_t
+    Rx, _, _ = kr.dconv_apply_ref(hv, None, p["w1"], p["b1"], st_y, L, p["g2w"], p["g2b"], p["scale"],
+                                  x.reshape(nb * L, C), False, False)
+    assert _close(Rx, xn_t.transpose(1, 2).reshape(nb * L, C).numpy())
+    rng = np.random.default_rng(C)
+    wr, br = rng.standard_normal((2 * C, C)) / np.sqrt(C), rng.standard_normal(2 * C)
+    xb = kr.bf16_round(Rx)
+    o_t = F.glu(F.conv1d(_t(xb.reshape(nb, L, C)).transpose(1, 2), _t(wr)[:, :, None], _t(br)), dim=1)
+    Ro, _ = kr.dconv_rewrite_ref(Rx, 0.0, wr, br)
+    assert _close(Ro, o_t.transpose(1, 2).reshape(nb * L, C).numpy())
+
+
+# ------------------------------------------------------------------------------------------------ emulations
+def _gelu_fast32(x):
+    """the tanh form x sigmoid(sqrt(8 / pi) (x + 0.044715 x^3)) in float32"""
+    x = x.astype(f32)
+    t = (f32(1.5957691216057308) * (x + f32(0.044715) * x * x * x)).astype(f32)
+    with np.errstate(over="ignore"):          # (exp overflows to inf for very negative x: x / inf = -0, as the kernel)
+        return (x / (f32(1) + np.exp(-t).astype(f32))).astype(f32)
+
+
+def _gelu32(x, fast):
+    if fast:
+        return _gelu_fast32(x)
+    return kr.gelu(x.astype(np.float64)).astype(f32)          # (the erf form: correctly rounded is honest enough)
+
+
+def _sigmoid32(g):
+    return (f32(1) / (f32(1) + np.exp(-g.astype(f32)).astype(f32))).astype(f32)
+
+
+def _gn32(v, gi, st, count, w, b):
+    m, r = kr.gn_params(st, count)
+    m, r = m.astype(f32)[gi][:, None], r.astype(f32)[gi][:, None]
+    return ((v.astype(f32) - m) * r * w.astype(f32) + b.astype(f32)).astype(f32)
+
+
+def _emu_conv3(x, w3, b3, dil, rows=16):
+    nb, L, C = x.shape
+    H = w3.shape[0]
+    wp = kr.conv3_pack(w3, max(rows, H)).astype(f32)
+    xp = np.zeros((nb, L + 4, C), dtype=f32)
+    xp[:, 2:2 + L] = x
+    acc = np.zeros((nb, L, wp.shape[0]), dtype=f32)
+    for t in range(3):                                         # one tap at a time, 32-wide K-steps
+        for k0 in range(0, C, 32):
+            k1 = min(k0 + 32, C)
+            acc = (acc + xp[:, 2 + (t - 1) * dil:2 + (t - 1) * dil + L, k0:k1] @ wp[:, t * C + k0:t * C + k1].T).astype(f32)
+    return (acc[..., :H] + b3.astype(f32)).astype(f32)
+
+
+def _emu_apply(hv, p, st_y, L, x, fast, out_bf16):
+    """the 1x1 on the packed GLU-interleaved weights, pair by pair"""
+    M, H = hv.shape
+    C = p["w1"].shape[0] // 2
+    wp = kr.conv1x1_pack(p["w1"]).astype(f32)
+    bp, gw, gb = (kr.glu_order(p[k]) for k in ("b1", "g2w", "g2b"))
+    hp = np.zeros((M, 64), dtype=f32)
+    hp[:, :H] = hv
+    y = (hp @ wp.T + bp.astype(f32)).astype(f32)
+    z = _gn32(y, np.arange(M) // L, st_y, L * 2 * C, gw, gb)
+    out = np.empty((M, C), dtype=f32)
+    for q in range(C // 16):
+        a, g = z[:, 32 * q:32 * q + 16], z[:, 32 * q + 16:32 * q + 32]
+        out[:, 16 * q:16 * q + 16] = x[:, 16 * q:16 * q + 16].astype(f32) + p["scale"][16 * q:16 * q + 16].astype(f32) * (a * _sigmoid32(g))
+    return kr.bf16_round(out) if out_bf16 else out.astype(np.float64)
+
+
+def _emu_rewrite(xb, wr, br):
+    M, C = xb.shape
+    wp = kr.rewrite_pack(wr).astype(f32)
+    K2 = wp.shape[1]
+    xk = np.zeros((M, K2), dtype=f32)
+    for k in range(K2):
+        if kr.rewrite_perm(k) < C:
+            xk[:, k] = xb[:, kr.rewrite_perm(k)]
+    y = (xk @ wp.T + kr.glu_order(br).astype(f32)).astype(f32)
+    out = np.empty((M, C), dtype=f32)
+    for q in range(C // 16):
+        out[:, 16 * q:16 * q + 16] = y[:, 32 * q:32 * q + 16] * _sigmoid32(y[:, 32 * q + 16:32 * q + 32])
+    return kr.bf16_round(out)
+
+
+def _emu_moments(x, gram, H):
+    """sum b + ws.x, sum b^2 + (2 v.x + x^T G x) per position in float32 from the product's packed moments"""
+    x = x.astype(f32)
+    G, v, ws = gram[:H * H].reshape(H, H), gram[H * H:H * H + H], gram[H * H + H:H * H + 2 * H]
+    q = np.zeros(x.shape[0], dtype=f32)
+    for j in range(H):
+        t = np.zeros(x.shape[0], dtype=f32)
+        for k in range(H):
+            t = (t + G[j, k] * x[:, k]).astype(f32)
+        q = (q + x[:, j] * t).astype(f32)
+    lv, lw = (x @ v).astype(f32), (x @ ws).astype(f32)
+    return (gram[-2] + lw).astype(np.float64), (gram[-1] + (f32(2) * lv + q)).astype(np.float64)
+
+
+@pytest.mark.parametrize("nb,L", td.C3_SHAPES)
+@pytest.mark.parametrize("dil", [1, 2])
+@pytest.mark.parametrize("C", [48, 96, 192, 384])
+def test_conv3_emulation_and_mutations(C, dil, nb, L):
+    H = C // 8
+    rng = np.random.default_rng(C + L + dil)
+    w3, bias = td._conv3_weights(C, C)
+    x = kr.bf16_round((rng.standard_normal((nb, L, C)) + 0.5) * td._rowscale(nb)[:, None, None])
+    R, tol = kr.dconv_conv3_ref(x, w3, bias, dil)
+    h = _emu_conv3(x, w3, bias, dil).astype(np.float64)
+    assert (np.abs(h - R) <= tol).all()
+    hs = h.reshape(nb * L, H)
+    sref, stol = kr.conv3_stats_ref(hs, L)
+    s32 = np.stack([hs.astype(f32).sum(1, dtype=f32).astype(np.float64).reshape(nb, L).sum(1),
+                    (hs.astype(f32) ** 2).sum(1, dtype=f32).astype(np.float64).reshape(nb, L).sum(1)], -1)
+    assert (np.abs(s32 - sref) <= stol).all()
+    # mutations (every swept L >= 16)
+    assert _exceeds(R, kr.dconv_conv3_ref(x, w3, bias, 3 - dil)[0], tol), "dil 1 <-> 2"
+    assert _exceeds(R, kr.dconv_conv3_ref(x, w3, bias, dil, mut="reversed")[0], tol), "taps reversed"
+    if nb > 1:
+        assert _exceeds(R, kr.dconv_conv3_ref(x, w3, bias, dil, mut="neighbour")[0], tol), "row end reads the neighbour"
+    if nb > 1 and L % 16:
+        assert _exceeds(sref, kr.conv3_stats_ref(hs, L, mut="unit_first")[0], stol), "straddling unit -> first row"
+
+
+@pytest.mark.parametrize("nb,L", td.MOM_SHAPES)
+@pytest.mark.parametrize("H", [6, 12, 24, 48])
+def test_moments_emulation_and_mutations(kt, H, nb, L):
+    rng = np.random.default_rng(H + L)
+    C = 8 * H
+    h = (rng.standard_normal((nb * L, H)) * np.repeat(td._rowscale(nb), L)[:, None] + 0.5).astype(f32)
+    h64 = h.astype(np.float64)
+    st = kr.group_sums(h64, L)
+    w, b = td._f32(1 + 0.25 * rng.standard_normal(H)), td._f32(0.1 * rng.standard_normal(H))
+    w1, b1 = td._mom_weights(H, rng)
+    R, tol = kr.gn_gelu_ref(h64, L, st, w, b)
+    x = kr.bf16_round(_gelu_fast32(_gn32(h, np.arange(nb * L) // L, st, L * H, w, b)))
+    assert (np.abs(x - R) <= tol).all()
+    sref, stol = kr.moment_stats_ref(x, L, kr.bf16_round(w1), b1)
+    s1, s2 = _emu_moments(x, kt.conv1x1_moments(w1, b1, True), H)
+    gi = np.arange(nb * L) // L
+    emu = np.stack([np.bincount(gi, s1), np.bincount(gi, s2)], -1)
+    assert (np.abs(emu - sref) <= stol).all(), (np.abs(emu - sref) / stol).max()
+    for mut in ("swap", "no2", "nob2") + (("boundary",) if nb > 1 else ()):
+        assert _exceeds(sref, kr.moment_stats_ref(x, L, kr.bf16_round(w1), b1, mut=mut)[0], stol), mut
+
+
+APPLY_SHAPES = [(L, M) for L in (1, 5, 16, 17, 64) for M in (1, 15, 16, 17, 100)]
+
+
+@pytest.mark.parametrize("L,M", APPLY_SHAPES)
+@pytest.mark.parametrize("C", [48, 96, 192, 384])
+def test_apply_emulation_and_mutations(C, L, M):
+    """Mutations are asserted for L >= 16 only: shorter GroupNorm rows can have a tiny variance, which inflates tol
+    legitimately (module docstring of kernel_refs), so a mutation need not stand out there."""
+    p = td._apply_weights(C, C, rewrite=C <= 96)
+    hb, x = td._apply_inputs(C, M, L, 7 * C + 1000 * L + M)
+    st = kr.group_sums(hb @ p["w1"].T + p["b1"], L)
+    args = (p["w1"], p["b1"], st, L, p["g2w"], p["g2b"], p["scale"], x, True, True)
+    R, tv, ts = kr.dconv_apply_ref(hb, None, *args)
+    got = _emu_apply(hb, p, st, L, x, True, True)
+    assert (np.abs(got - R) <= ts).all(), (np.abs(got - R) / ts).max()
+    if C <= 96:
+        Ro, to = kr.dconv_rewrite_ref(R, tv, p["wr"], p["br"])
+        go = _emu_rewrite(got, p["wr"], p["br"])
+        assert (np.abs(go - Ro) <= to).all(), (np.abs(go - Ro) / to).max()
+    if L < 16:
+        return
+    for mut in ("swap", "gate_tile", "scale_packed", "no_res"):
+        assert _exceeds(R, kr.dconv_apply_ref(hb, None, *args, mut=mut)[0], ts), mut
+    if L % 16 and M > L:                  # (a 16-row unit that straddles two rows)
+        assert _exceeds(R, kr.dconv_apply_ref(hb, None, *args, mut="unit_first")[0], ts), "unit_first"
+    if C <= 96:
+        assert _exceeds(Ro, kr.dconv_rewrite_ref(R, tv, p["wr"], p["br"], mut="natural_k")[0], to), "natural K order"
+
+
+@pytest.mark.parametrize("nb,L", td.DS_SHAPES)
+@pytest.mark.parametrize("dil", [1, 2])
+@pytest.mark.parametrize("fast", [0, 1])
+@pytest.mark.parametrize("xb", [0, 1])
+@pytest.mark.parametrize("C", [48, 96])
+def test_small_emulation(kt, C, xb, fast, dil, nb, L):
+    """dconv_small's three passes in float32 (natural-order weights, sequential accumulation), staged like the GPU test"""
+    H = C // 8
+    p = td._small_weights(C, C + fast)
+    rng = np.random.default_rng(100 * L + nb + dil)
+    x = (rng.standard_normal((nb, L, C)) + 0.25) * td._rowscale(nb)[:, None, None]
+    x = kr.bf16_round(x) if xb else td._f32(x)
+    R, tol = kr.dconv_conv3_ref(x, p["w3"], p["b3"], dil)
+    h32 = _emu_conv3(x, p["w3"], p["b3"], dil, rows=H)
+    assert (np.abs(h32 - R) <= tol).all()
+    h = h32.astype(np.float64).reshape(nb * L, H)
+    st_h = kr.group_sums(h, L)
+    gi = np.arange(nb * L) // L
+    hv32 = _gelu32(_gn32(h32.reshape(nb * L, H), gi, st_h, L * H, p["g1w"], p["g1b"]), fast)
+    hv, dh = kr.gn_gelu_ref(h, L, st_h, p["g1w"], p["g1b"], fast=bool(fast), out_bf16=False)
+    assert (np.abs(hv32 - hv) <= dh).all()
+    yref, ytol = kr.moment_stats_ref(hv, L, p["w1"], p["b1"], d=dh)
+    s1, s2 = _emu_moments(hv32, kt.conv1x1_moments(p["w1"], p["b1"], False), H)
+    emu = np.stack([np.bincount(gi, s1), np.bincount(gi, s2)], -1)
+    assert (np.abs(emu - yref) <= ytol).all(), (np.abs(emu - yref) / ytol).max()
+    Rx, tv, ts = kr.dconv_apply_ref(hv, dh, p["w1"], p["b1"], emu, L, p["g2w"], p["g2b"], p["scale"],
+                                    x.reshape(nb * L, C), bool(fast), bool(xb))
+    y32 = (hv32 @ p["w1"].astype(f32).T + p["b1"].astype(f32)).astype(f32)
+    z = _gn32(y32, gi, emu, L * 2 * C, p["g2w"], p["g2b"])
+    o = (x.reshape(nb * L, C).astype(f32) + p["scale"].astype(f32) * (z[:, :C] * _sigmoid32(z[:, C:]))).astype(f32)
+    got = kr.bf16_round(o) if xb else o.astype(np.float64)
+    assert (np.abs(got - Rx) <= ts).all(), (np.abs(got - Rx) / ts).max()
+
+
+def test_bf16_round_amb_with_bound():
+    """an element within d of a tie gets one ulp, others 0; a tiny element (and 0) gets about d"""
+    tie = 1.0 + 2.0 ** -8                       # halfway between 1 and 1 + 2^-7
+    a = np.array([tie - 1e-4, tie - 1e-2 * 2.0 ** -7, 1.0 + 2.0 ** -10, 2.0 ** -20 * 1.3, 0.0])
+    r, amb = kr.bf16_round_amb(a, 2e-4)
+    assert amb[0] == 2.0 ** -7 and amb[1] == 2.0 ** -7 and amb[2] == 0.0
+    assert 2e-4 - 2.0 ** -20 <= amb[3] <= 2e-4 + 2.0 ** -20 and 2e-4 - 2.0 ** -20 <= amb[4] <= 2e-4 + 2.0 ** -20
+    # whatever a kernel within d computed, its rounding lies within amb of the reference's
+    rng = np.random.default_rng(5)
+    x = rng.standard_normal(20000) * 2.0 ** rng.integers(-12, 3, 20000)
+    d = 3e-6
+    r, amb = kr.bf16_round_amb(x, d)
+    for s in (-1.0, 1.0, 0.37):
+        assert (np.abs(kr.bf16_round(x + s * d) - r) <= amb).all()
+
+
+# ------------------------------------------------------------------------------------------------ fenc_row
+def _onepass32(s1, s2, n):
+    """gn_from_sums in float32"""
+    m = f32(s1) / f32(n)
+    var = f32(s2) / f32(n) - m * m
+    var = f32(0) if var < 0 else var
+    return m, f32(1) / np.sqrt(var + f32(1e-5), dtype=f32)
+
+
+def _emu_fenc_row(kt, level, p, xin, a_norm, f, Fin, row_add):
+    """one row of a level in float32: bf16 x image and hidden tile, one-pass f32 statistics, the 1x1 statistics from
+    the packed moments, the folded GroupNorm -> GLU affine with exp2"""
+    T, Cin = xin.shape[1], xin.shape[2]
+    C = p["wc"].shape[0]
+    H = C // 8
+    a = np.zeros((T, 8, Cin), dtype=f32)
+    for tap in range(8):
+        fi = 4 * f - 2 + tap
+        if 0 <= fi < Fin:
+            if level == 0:
+                rdv = f32(1) / f32(a_norm[1])
+                a[:, tap] = kr.bf16_round(((xin[fi].astype(f32) - f32(a_norm[0])) * rdv).astype(f32))
+            else:
+                a[:, tap] = xin[fi]
+    wc = np.transpose(p["wc"], (0, 2, 1)).reshape(C, 8 * Cin).astype(f32)
+    x = _gelu_fast32((a.reshape(T, -1) @ wc.T + p["bc"].astype(f32)).astype(f32))
+    L2E = f32(-1.4426950408889634)
+    for dd in range(2):
+        q = p["dc"][dd]
+        xb = kr.bf16_round(x)
+        h = _emu_conv3(xb[None], q["w3"], q["b3"], 1 << dd)[0]
+        hm, hr = _onepass32(h.sum(dtype=f32), (h * h).sum(dtype=f32), H * T)
+        hb = kr.bf16_round(_gelu_fast32(((h - hm) * hr * q["g1w"].astype(f32) + q["g1b"].astype(f32)).astype(f32))).astype(f32)
+        s1, s2 = _emu_moments(hb, kt.conv1x1_moments(q["w1"], q["b1"], True), H)
+        ym, yr = _onepass32(s1.astype(f32).sum(dtype=f32), s2.astype(f32).sum(dtype=f32), 2 * C * T)
+        y = (hb @ q["w1"].astype(f32).T).astype(f32)
+        w_ = (q["g2w"].astype(f32) * yr).astype(f32)
+        c_ = ((q["b1"].astype(f32) - ym) * w_ + q["g2b"].astype(f32)).astype(f32)
+        sc = q["scale"].astype(f32)
+        av = (y[:, :C] * (w_[:C] * sc) + c_[:C] * sc).astype(f32)
+        gv = (y[:, C:] * (w_[C:] * L2E) + c_[C:] * L2E).astype(f32)
+        x = (av * (f32(1) / (f32(1) + np.exp2(gv).astype(f32))) + x).astype(f32)
+    xb = kr.bf16_round(x).astype(f32)
+    y = (xb @ p["wr"].astype(f32).T + p["br"].astype(f32)).astype(f32)
+    o = (y[:, :C] * _sigmoid32(y[:, C:])).astype(f32)
+    if row_add is not None:
+        o = (o + row_add[f].astype(f32)).astype(f32)
+    return kr.bf16_round(o)
+
+
+FENC_CPU = [(T, 2, 4) for T in td.FENC_T] + [(17, 1, 1), (259, 1, 3), (17, 3, 3)]
+
+
+@pytest.mark.parametrize("T,Fout", [(5, 1), (17, 2), (49, 3)])
+@pytest.mark.parametrize("level", [0, 1])
+def test_fenc_row_ref_equals_functional(level, T, Fout):
+    """fenc_row_ref against torch.nn.functional in float64 with the bf16 roundings at the documented points (the conv
+    input of level 0, the x image before each conv3 and before the rewrite, the hidden tile): Conv2d (8,1) / (4,1) /
+    (2,0) over frequency -> gelu(tanh) -> 2 x [conv1d k3 dilation 1, 2 -> group_norm(1) -> gelu(tanh) -> conv1d k1 ->
+    group_norm(1) -> glu -> LayerScale -> residual] -> conv1d k1 -> glu (+ embedding row)"""
+    import torch.nn.functional as F
+    cin, C = td.FENC_DIMS[level]
+    p = td._fenc_weights(level)
+    x, a_norm, row_add = td._fenc_inputs(level, 1, Fout, T, 3 * T + Fout + level)
+    if level == 1:
+        row_add = None
+    a = kr.bf16_round((x[0] - a_norm[0, 0]) / a_norm[0, 1]) if level == 0 else x[0]              # [Fin][T][cin]
+    rnd = lambda t: _t(kr.bf16_round(t.numpy()))
+    y = F.conv2d(_t(a).permute(2, 0, 1)[None], _t(p["wc"])[..., None], _t(p["bc"]), stride=(4, 1), padding=(2, 0))
+    xs = F.gelu(y, approximate="tanh")[0].permute(1, 0, 2)                                       # [Fout][C][T]
+    for dd in range(2):
+        q = p["dc"][dd]
+        h = F.conv1d(rnd(xs), _t(q["w3"]), _t(q["b3"]), padding=1 << dd, dilation=1 << dd)
+        hv = rnd(F.gelu(F.group_norm(h, 1, _t(q["g1w"]), _t(q["g1b"]), eps=1e-5), approximate="tanh"))
+        z = F.group_norm(F.conv1d(hv, _t(q["w1"])[..., None], _t(q["b1"])), 1, _t(q["g2w"]), _t(q["g2b"]), eps=1e-5)
+        xs = xs + _t(q["scale"])[None, :, None] * F.glu(z, dim=1)
+    o = F.glu(F.conv1d(rnd(xs), _t(p["wr"])[..., None], _t(p["br"])), dim=1)
+    if row_add is not None:
+        o = o + _t(row_add)[:, :, None]
+    R, _ = td._fenc_ref(level, p, x, a_norm, row_add)
+    assert _close(R[0], o.permute(0, 2, 1).numpy())
+
+
+# Which mutations the end-to-end bound separates (more than 10x outside somewhere), measured on FENC_CPU; the figures
+# are the largest |mutated - R| / tol of a shape.
+#   level 0, T >= 16, Fout > 1: tap_shift 40 .. 2900, emb_next 20 .. 560, out4 18 .. 1700: asserted.
+#   level 0, (T, B, Fout) = (17, 1, 1): tap_shift 1.7, out4 4.5 (one row, both of its neighbours outside [0, Fin), so
+#     the shifted taps read three zero rows instead of two): not separated.
+#   level 0, count_pad: 0.06 .. 4.5 for T >= 16 (0 where T is a multiple of 16: the mutation is the identity), 7 .. 134
+#     only for T <= 3: a count off by 5 % moves the output less than the bound.  Not separated.
+#   level 1: the bound is vacuous (median 9e2 .. 7e3 for outputs of rms 1; the float32 emulation sits at 1e-6 .. 2e-4
+#     of it): K = 384 gives the conv a bound of 1.8e-4, 44 % of the first image lies within it of a tie, and after
+#     the first DConv layer every element does.  No mutation is separated (tap_shift 6e-4 .. 37).
+FENC_SEPARATED = {0: ("tap_shift", "emb_next", "out4"), 1: ()}
+
+
+@pytest.mark.parametrize("T,B,Fout", FENC_CPU)
+@pytest.mark.parametrize("level", [0, 1])
+def test_fenc_row_emulation_and_mutations(kt, level, T, B, Fout):
+    """The float32 emulation stays inside the end-to-end bound on every row.  The mutations of FENC_SEPARATED land more
+    than 10x outside it for T >= 16 and Fout > 1 (shorter rows are exempt: their tiny GroupNorm variance inflates the
+    bound legitimately); the others are evaluated and their distance printed, and where the table above says a
+    mutation is not separated the test asserts just that, so a tighter bound shows up here as a failure to update."""
+    p = td._fenc_weights(level)
+    x, a_norm, row_add = td._fenc_inputs(level, B, Fout, T, 31 * T + 7 * B + Fout + level)
+    if level == 1:
+        row_add = None
+    Fin = 4 * Fout
+    R, tol = td._fenc_ref(level, p, x, a_norm, row_add)
+    worst = 0.0
+    for b in range(B):
+        for f in range(Fout):
+            got = _emu_fenc_row(kt, level, p, x[b], None if a_norm is None else a_norm[b], f, Fin, row_add)
+            worst = max(worst, float((np.abs(got - R[b, f]) / tol[b, f]).max()))
+    assert worst <= 1.0, worst
+    dist = {"out4": float((np.abs(R[..., 4:8] - R[..., :4]) / tol[..., :4]).max())}
+    for mut in ("tap_shift", "count_pad") + (("emb_next",) if row_add is not None and Fout > 1 else ()):
+        dist[mut] = float((np.abs(td._fenc_ref(level, p, x, a_norm, row_add, mut=mut)[0] - R) / tol).max())
+    print("fenc_row level %d T=%d B=%d Fout=%d: emulation %.3g, mutations %s" % (level, T, B, Fout, worst, dist))
+    if T < 16 or Fout < 2:
+        return
+    for mut in dist:
+        if mut in FENC_SEPARATED[level]:
+            assert dist[mut] > 10.0, (mut, dist[mut])
+    assert dist["count_pad"] <= 10.0, dist["count_pad"]
+    if level == 1:
+        assert np.median(tol) > 100.0          # (vacuous: see the table above)
