@@ -206,7 +206,8 @@ def build_gemm(seed, mode, *, nb, H_in, W=1, C_in, N, ntaps=1, in_stride=1, in_o
                flat=False, a_norm=False, a_gn=False, Kp=None, bias=True, c_bf16=0, act=kr.ACT_NONE, res=None,
                res_bf16=0, res_scale=False, res_gn=False, row_add=False, stats=False, gn=False, store=1, c4=False,
                convt=None, pbias=False, pfold=1, res_div=1, ln=None, sk=False):
-    """A forward.cpp call-site form at reduced size, as a kernel_refs.gemm_spec with host arrays."""
+    """A call-site form of the forward (csrc/forward_*.cpp) at reduced size, as a kernel_refs.gemm_spec with host
+    arrays."""
     rng = np.random.default_rng(seed)
     H_out = H_in if H_out is None else H_out
     K = ntaps * C_in
@@ -241,7 +242,7 @@ def build_gemm(seed, mode, *, nb, H_in, W=1, C_in, N, ntaps=1, in_stride=1, in_o
     Nout = N // 2 if act == kr.ACT_GLU else N
     g.ldo = Nout
     g.H_out_total = H_out
-    if convt is not None:      # ConvTranspose residue groups of cout columns (forward.cpp conv_t)
+    if convt is not None:      # ConvTranspose residue groups of cout columns (forward_dec.cpp conv_t)
         kind, keep = convt
         cout = N // 4 if kind == "quad" else N // 2
         g.col_split, g.ldo = cout, cout
@@ -406,7 +407,7 @@ def _case(name, mode, expect=None, **kw):
     GEMM_CASES[name] = (mode, expect, kw)
 
 
-# dense linear layers (forward.cpp lin()): upsampler, q / kv / qkv, linear1, text.mlp0, downsampler
+# dense linear layers (forward.h lin()): upsampler, q / kv / qkv, linear1, text.mlp0, downsampler
 for _nb, _h in _m_edges(256):
     _case("upsampler[%dx%d]" % (_nb, _h), 1, "GEMM5", nb=_nb, H_in=_h, C_in=384, N=512)
     _case("qkv[%dx%d]" % (_nb, _h), 1, "GEMM5", nb=_nb, H_in=_h, C_in=512, N=1536, c_bf16=1)
@@ -461,7 +462,7 @@ for _nb, _h, _w in [(1, 16, 8), (1, 43, 3), (3, 23, 3)]:
 for _nb, _h in _m_edges(128):
     _case("tenc.conv.l1[%dx%d]" % (_nb, _h), 1, "GEMM2", nb=_nb, H_in=4 * _h - 1, H_out=_h, C_in=48, N=96, ntaps=8,
           in_stride=4, in_off=-2, c_bf16=1, act=kr.ACT_GELU)
-# ConvTranspose residues as GEMM column groups (forward.cpp conv_t): quad (k_blk) and pairs, all rows / kept rows
+# ConvTranspose residues as GEMM column groups (forward_dec.cpp conv_t): quad (k_blk) and pairs, all rows / kept rows
 for _keep in (0, 1):
     for _nb, _h, _w in [(1, 8, 31), (3, 8, 11)]:
         _case("convt.quad.c192.keep%d[%dx%dx%d]" % (_keep, _nb, _h, _w), 1, "GEMM3_V7", nb=_nb, H_in=_h, W=_w, C_in=192,
@@ -489,9 +490,9 @@ _case("v1.f32.glu.res[3x69]", 0, "V1_F32", nb=3, H_in=69, C_in=24, N=96, Kp=32, 
 
 @pytest.mark.parametrize("name", sorted(GEMM_CASES))
 def test_gemm(kt, name):
-    """gemm_launch on one forward.cpp call-site form at reduced size: tol = (K + 16) e S propagated through the
-    epilogue (kernel_refs.gemm_ref), statistics by the sum rule; the route is recorded and, where the form pins it,
-    asserted"""
+    """gemm_launch on one call-site form of the forward (csrc/forward_*.cpp) at reduced size: tol = (K + 16) e S
+    propagated through the epilogue (kernel_refs.gemm_ref), statistics by the sum rule; the route is recorded and,
+    where the form pins it, asserted"""
     mode, expect, kw = GEMM_CASES[name]
     g = build_gemm(sum(map(ord, name)), mode, **kw)
     route = run_gemm(kt, g, mode, "gemm[%s]" % name)

@@ -338,8 +338,8 @@ def test_decode_chunks_match_one_chunk(models):
 def test_decode_chunks_per_item_prompts(models, dt):
     """athd_forward with a DIFFERENT prompt per segment over 5 decode chunks of one item each: every chunk rewrites
     the prompt row vectors (text_vec_kernel) and every other chunk the freq output buffer, while the previous
-    chunk's time branch and iSTFT may still run on the second stream (forward.cpp decode_chunk orders both with
-    ev_t).  Equals one chunk (f32: fp32 rounding; bf16: >= 40 dB, order-dependent statistics)."""
+    chunk's time branch and iSTFT may still run on the second stream (forward_dec.cpp decode_chunk orders both with
+    ev_t, forward.h StreamPlan::chunk_record_time / chunk_wait_time).  Equals one chunk (f32: fp32 rounding; bf16: >= 40 dB, order-dependent statistics)."""
     from athd.synth import synthetic_batch
     wav = torch.as_tensor(synthetic_batch(5, 40000, seed0=78)).cuda()
     prompts = ["drums", "vocals", "bass", "other", "vocals"]
@@ -356,6 +356,34 @@ def test_decode_chunks_per_item_prompts(models, dt):
     else:
         for i in range(5):
             assert sdr_db(one[i].cpu().numpy(), many[i].cpu().numpy()) >= 40.0, i
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_serial_matches_two_streams(models, dt, monkeypatch):
+    """ATHD_SERIAL=1 (both branches on the caller's stream; read at every forward, forward.h Switches) == the
+    two-stream forward over 3 decode chunks (3 segments x 4 prompts, 4 items per chunk: the cross-chunk ordering and
+    the double-buffered freq output).  Same computation, different scheduling: the tolerances of
+    test_graph_replay_matches_eager (f32: fp32 rounding of the order-dependent fp64 statistics atomics; bf16:
+    >= 40 dB).  The count of differing outputs is reported, not asserted."""
+    from athd.synth import synthetic_batch
+    wav = torch.as_tensor(synthetic_batch(3, 40000, seed0=77)).cuda()
+    prompts = ["drums", "bass", "other", "vocals"]
+    m = models[dt]
+    m.set_decode_items(4)                           # 3 chunks of one segment x 4 prompts
+    try:
+        monkeypatch.delenv("ATHD_SERIAL", raising=False)
+        two = m.forward_prompts(wav, prompts)
+        monkeypatch.setenv("ATHD_SERIAL", "1")
+        one = m.forward_prompts(wav, prompts)
+        torch.cuda.synchronize()
+    finally:
+        m.set_decode_items(None)
+    _report(f"serial_vs_two_streams/{dt}", {"differing_outputs": int((two != one).sum().item()),
+                                            "outputs": two.numel()})
+    if dt == "f32":
+        assert torch.allclose(one, two, atol=1e-5, rtol=1e-4)
+    else:
+        assert sdr_db(two.cpu().numpy(), one.cpu().numpy()) >= 40.0
 
 
 def test_bench_batch_one_chunk(models, oracle_model, text_table):
