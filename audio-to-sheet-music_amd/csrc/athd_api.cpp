@@ -140,7 +140,7 @@ const std::vector<std::pair<std::string, std::vector<int64_t>>>& keys() {
 // =============================================================================================== ABI
 extern "C" {
 
-int athd_version(void) { return 101; }
+int athd_version(void) { return 102; }
 
 int athd_num_required_keys(void) { return (int)keys().size(); }
 
@@ -548,6 +548,27 @@ int athd_sdr(const float* est, const float* target, int64_t rows, int64_t n, dou
 int athd_sisdr(const float* est, const float* target, int64_t rows, int64_t n, double* scratch, float* out,
                void* stream) {
     const int rc = sisdr_launch(est, target, rows, n, scratch, out, (hipStream_t)stream);
+    return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : ATHD_EHIP);
+}
+
+int64_t athd_resample_length(int64_t length, int orig_freq, int new_freq) {
+    return resample_length(length, orig_freq, new_freq);
+}
+
+size_t athd_resample_scratch_bytes(int orig_freq, int new_freq) { return resample_scratch_bytes(orig_freq, new_freq); }
+
+int athd_resample(const float* in, int64_t length, int in_channels, int64_t frame_stride, int64_t channel_stride,
+                  int orig_freq, int new_freq, float* out, int out_channels, void* scratch, size_t scratch_bytes,
+                  void* stream) {
+    const int rc = resample_launch(in, length, in_channels, frame_stride, channel_stride, orig_freq, new_freq, out,
+                                   out_channels, scratch, scratch_bytes, (hipStream_t)stream);
+    return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : (rc == -5 ? ATHD_EWORKSPACE : ATHD_EHIP));
+}
+
+int64_t athd_spectrogram_frames(int64_t T) { return spectrogram_frames(T); }
+
+int athd_spectrogram_db(const float* wav, int channels, int64_t T, float* out, void* stream) {
+    const int rc = spectrogram_db_launch(wav, channels, T, out, (hipStream_t)stream);
     return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : ATHD_EHIP);
 }
 

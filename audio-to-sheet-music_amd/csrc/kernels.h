@@ -232,4 +232,13 @@ int sdr_launch(const float* est, const float* tgt, int64_t rows, int64_t n, doub
 int sisdr_launch(const float* est, const float* tgt, int64_t rows, int64_t n, double* scratch, float* out,
                  hipStream_t s);
 
+// audio_io.hip: torchaudio-default resampler (band-table form) and the dB spectrogram of app.py:74-94.
+// resample_launch returns -1 (bad argument / unsupported pair), -5 (scratch too small) or a HIP error
+int64_t resample_length(int64_t length, int orig, int nw);
+size_t resample_scratch_bytes(int orig, int nw);
+int resample_launch(const float* in, int64_t L, int in_ch, int64_t fs, int64_t cs, int orig, int nw, float* out,
+                    int out_ch, void* scratch, size_t scratch_bytes, hipStream_t s);
+int64_t spectrogram_frames(int64_t T);
+int spectrogram_db_launch(const float* wav, int channels, int64_t T, float* out, hipStream_t s);
+
 }  // namespace athd

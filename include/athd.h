@@ -123,6 +123,49 @@ int athd_sdr(const float* est, const float* target, int64_t rows, int64_t n, dou
 int athd_sisdr(const float* est, const float* target, int64_t rows, int64_t n, double* scratch, float* out,
                void* stream);
 
+/* ---- Audio front end: the user path of app.py:74-126 (a file of any rate, mono or stereo) ----
+ * Stream-only like the track level: no context, no host synchronisation, no device allocation, work enqueued on
+ * `stream`.
+ *
+ * Resampler = torchaudio.transforms.Resample(orig_freq, new_freq) with its defaults (sinc_interp_hann,
+ * lowpass_filter_width = 6, rolloff = 0.99):
+ *   g = gcd(orig, new), o = orig / g, n = new / g, base = min(o, n) * 0.99, w = ceil(6 o / base);
+ *   the table K[i][k] has n phases i and 2 w + o taps k, computed in double and rounded once to fp32:
+ *     t = clamp((-i / n + (k - w) / o) * base, -6, 6),  K = sinc(pi t) * cos^2(pi t / 12) * base / o,  sinc(0) = 1;
+ *   y[j n + i] = sum_k xpad[j o + k] K[i][k] with xpad[m] = x[m - w], zero outside the signal;
+ *   the output has athd_resample_length() = ceil(n * length / o) samples per channel.
+ * The taps outside the Hann window's support are exact zeros in the fp32 table, so the sum runs over the live band of
+ * each phase only (at most 14 taps for sources up to 48 kHz -> 44.1 kHz), as fp32 FMAs in ascending tap order from
+ * 0.0f: the result is the same bits on every run.
+ *
+ * Supported pairs: the band table (n first-tap indices + n rows of NT coefficients, NT rounded up to odd) must fit in
+ * 40 KiB (it is held in LDS beside the staged input) and o + 2 w <= 6144.  That covers every common rate (8 .. 192
+ * kHz <-> 44.1 / 48 kHz); a near co-prime pair such as 44101 -> 44100 is not supported: athd_resample_scratch_bytes
+ * returns 0 and athd_resample ATHD_EINVAL.  orig == new is always supported (a de-interleave / duplicate pass that
+ * leaves the scratch untouched).
+ *
+ * in: device f32, sample (frame t, channel c) at in[t * frame_stride + c * channel_stride] (strides in elements:
+ * (channels, 1) reads a WAV's interleaved frames, (1, length) a planar tensor).  out: device f32, planar
+ * (out_channels, athd_resample_length()).  out_channels == in_channels, or in_channels == 1 and the one channel is
+ * duplicated into every output channel (app.py:123-124).  scratch: device, athd_resample_scratch_bytes() bytes
+ * (the host builds the table once per pair and copies it there on `stream` in every call; ATHD_EWORKSPACE if too
+ * small).  The first call for a rate pair page-locks its copy of the table (one host allocation per pair and
+ * process); from then on the call only enqueues a copy and a kernel and can be captured in a graph. */
+int64_t athd_resample_length(int64_t length, int orig_freq, int new_freq);
+size_t athd_resample_scratch_bytes(int orig_freq, int new_freq);
+int athd_resample(const float* in, int64_t length, int in_channels, int64_t frame_stride, int64_t channel_stride,
+                  int orig_freq, int new_freq, float* out, int out_channels, void* scratch, size_t scratch_bytes,
+                  void* stream);
+
+/* dB spectrogram of app.py:74-94: mono = mean of the channels (one channel is used as is),
+ * torch.stft(n_fft = 2048, hop_length = 512) with its defaults (rectangular window, center = True with a reflect pad
+ * of 1024, one-sided), 20 log10(|X| + 1e-8).  wav: device planar (channels, T) f32 -> out: device
+ * (1025, athd_spectrogram_frames(T) = 1 + T / 512) f32, frequency-major as torch returns it.  The FFT runs in fp32;
+ * |X|, the logarithm and the factor 20 are evaluated in double on that spectrum and rounded once to fp32.
+ * T <= 1024 returns ATHD_EINVAL (torch's reflect pad fails there too). */
+int64_t athd_spectrogram_frames(int64_t T);
+int athd_spectrogram_db(const float* wav, int channels, int64_t T, float* out, void* stream);
+
 /* Kernel timing (measurement aid for bench.py; not part of the reference interface).  Between
  * athd_profile_start and athd_profile_stop every launch of kernel `kernel` (its rocprofv3 symbol without
  * "void athd::", the argument list and 'u' suffixes, e.g. "attn_bf16_kernel"; NULL or "" = all kernels) made
