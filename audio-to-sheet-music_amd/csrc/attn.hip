@@ -16,9 +16,7 @@ namespace athd {
 // per XCD.  All query blocks of a (b, h) then run on one XCD at about the same time and its K / V come from HBM
 // once into that XCD's L2, instead of once per XCD they were spread over.
 ATHD_DEV void attn_tile(const AttnDesc& d, int& qb, int& h, int64_t& b, int qblock = 128) {
-    const int n = (int)gridDim.x, i = (int)blockIdx.x;
-    const int q = n / 8, r = n % 8, x = i % 8;
-    const int t = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i / 8;
+    const int t = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int gq = (d.Nq + qblock - 1) / qblock;
     qb = t % gq;
     const int bh = t / gq;

@@ -109,6 +109,14 @@ ATHD_DEV float wave_max(float v) {
     return v;
 }
 
+// XCD-aware block order (cdna_hip_programming.md T1): workgroup i runs on XCD i % 8, so logical ids are handed out as
+// 8 contiguous ranges, one per XCD (bijective for any n) - neighbouring ids share operands in that XCD's L2.
+// Returns the logical id of workgroup i of n.
+ATHD_DEV int xcd_remap(int i, int n) {
+    const int q = n / 8, r = n % 8, x = i % 8;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i / 8;
+}
+
 // PyTorch-faithful fp32 source index for linear/bilinear resize with align_corners=False and no explicit scale
 // (ATen UpSample.h area_pixel_compute_scale / area_pixel_compute_source_index / guard_index_and_lambda).
 struct LinIdx { int i0, i1; float l0, l1; };

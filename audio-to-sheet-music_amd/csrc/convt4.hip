@@ -23,6 +23,7 @@
 #include "common.h"
 #include "prof.h"
 #include "gemm.h"
+#include "gemm_tile.h"
 #include "kernels.h"
 
 
@@ -34,9 +35,6 @@ constexpr int CT_CI = 96, CT_CO = 48;
 constexpr int CT_KP = 2 * CT_CI;           // pair-local K: [lower tap row | upper tap row]
 constexpr int CT_WROW = CT_KP * 2;         // 384 B per weight row in LDS
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16v8;
-
-__device__ __attribute__((aligned(64))) uint4 g_zero_ct4[4];
 __device__ uint2 g_sink_ct4[64];          // store target of rows past M (branch-free epilogue)
 
 }  // namespace
@@ -87,7 +85,7 @@ __global__ __launch_bounds__(NW * 64) void convt4_kernel(const ConvT4Desc d) {
     };
 
     const char* const xb = reinterpret_cast<const char*>(d.x);
-    const char* const zero = reinterpret_cast<const char*>(g_zero_ct4);
+    const char* const zero = reinterpret_cast<const char*>(g_zero_page);
     const int64_t rowW = (int64_t)d.W * (CT_CI * 2);      // bytes between input rows u and u+1
     const int H = d.H;
     uint2* const sink = g_sink_ct4 + lane;
@@ -310,7 +308,7 @@ __global__ __launch_bounds__(CW_NW * 64) void convt4_walk_kernel(const ConvT4Des
         return *reinterpret_cast<const bf16v8*>(wl + a);
     };
     const char* const xb = reinterpret_cast<const char*>(d.x);
-    const char* const zero = reinterpret_cast<const char*>(g_zero_ct4);
+    const char* const zero = reinterpret_cast<const char*>(g_zero_page);
     const f32x4_t z4 = {0.f, 0.f, 0.f, 0.f};
     // one residue rho at a time (its 3 channel tiles: pair p = rho / 2, pair-local tiles 3 (rho & 1) ..): each weight
     // fragment feeds RF MFMAs, and only 3 x RF accumulators are live

@@ -59,11 +59,6 @@ ATHD_HD int g_tb(int qi, int T, int Qg) { return (int)((int64_t)T * qi / Qg); }
 
 ATHD_DEV int swz(int row, int chunk) { return row * 256 + ((chunk ^ (row & 15)) << 4); }
 
-ATHD_DEV int g_xcd_remap(int i, int n) {
-    const int q = n / 8, r = n % 8, x = i % 8;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i / 8;
-}
-
 // the Gram blocks of a wave (10 each): half 0 of a class takes rows R0 (columns 0..5), R3 (3..5) and R4 (5), half 1
 // rows R1 (1..5), R2 (2..5) and R4 (4); column 5 = the one-hot channel matrix
 constexpr int G_NBLK = 10;
@@ -134,7 +129,7 @@ __global__ __launch_bounds__(G_THREADS, 1) void fdec1_gram_kernel(const LowRankD
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nblk = (int)gridDim.x;
-    const int L = g_xcd_remap((int)blockIdx.x, nblk);
+    const int L = xcd_remap((int)blockIdx.x, nblk);
     const int g = L % G_NG, qi = L / G_NG, Qg = (nblk - 1 - g) / G_NG + 1;
     const int c0 = g * G_CG;
     const int W = d.W;

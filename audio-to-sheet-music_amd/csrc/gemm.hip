@@ -10,10 +10,7 @@
 // tile t and written to the other LDS buffer after them; one barrier per k-step.
 #include <cstdlib>
 
-#include "common.h"
-#include "prof.h"
-#include "gemm.h"
-#include "gemm_epi.h"
+#include "gemm_launch.h"
 
 namespace athd {
 
@@ -259,12 +256,7 @@ static void launch_cfg(const GemmDesc& d, hipStream_t s) {
     const int64_t M = (int64_t)d.nb * d.H_out * d.W;
     dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)((d.N + BN - 1) / BN));
     const bool vec8 = (d.C_in % 8 == 0) && (d.a_ld % 8 == 0) && d.a_cs == 1;
-    KScope ks(s);
-    if (ks.on()) {
-        double fl, by;
-        gemm_work(d, MODE, fl, by);
-        ks.begin(klabel("gemm_kernel<%d,%d,%d,%d,%d,%s>", MODE, BM, BN, WM, WN, vec8 ? "true" : "false"), fl, by);
-    }
+    GemmScope ks(s, d, MODE, "gemm_kernel<%d,%d,%d,%d,%d,%s>", MODE, BM, BN, WM, WN, vec8 ? "true" : "false");
     if (vec8) hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, true>), grid, dim3(256), 0, s, with_fastdiv(d));
     else hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, WM, WN, false>), grid, dim3(256), 0, s, with_fastdiv(d));
 }
@@ -276,24 +268,6 @@ static void launch_mode(const GemmDesc& d, hipStream_t s) {
     else if (d.N <= 64) launch_cfg<MODE, 128, 64, 2, 2>(d, s);
     else launch_cfg<MODE, 128, 128, 2, 2>(d, s);
 }
-
-bool gemm2_supported(const GemmDesc& d);
-int gemm2_launch(const GemmDesc& d, hipStream_t s);
-bool gemm3_supported(const GemmDesc& d);
-int gemm3_launch(const GemmDesc& d, hipStream_t s, int variant);
-bool gemm3_ln_supported(const GemmDesc& d);
-int gemm3_ln_launch(const GemmDesc& d, hipStream_t s);
-bool gemm5_supported(const GemmDesc& d);
-int gemm5_launch(const GemmDesc& d, hipStream_t s);
-
-bool rowln_supported(const GemmDesc& d);
-int rowln_launch(const GemmDesc& d, hipStream_t s);
-bool rowln_text_enabled();
-bool rowln_text_supported(const GemmDesc& d);
-int rowln_text_launch(const GemmDesc& d, hipStream_t s);
-#ifdef ATHD_KBENCH
-int gemm6_launch(const GemmDesc& d, hipStream_t s);
-#endif
 
 // The dispatch of gemm_launch as a pure function of the descriptor (and ATHD_RLT): the route, or ROUTE_REFUSED.
 int gemm_route(const GemmDesc& d, int mode) {
@@ -334,15 +308,16 @@ int gemm_launch(const GemmDesc& d0, int mode, hipStream_t s) {
         if (rc != -2) return rc;
     }
 #endif
-    switch (gemm_route(d, mode)) {
+    const GemmRoute route = (GemmRoute)gemm_route(d, mode);
+    switch (route) {
         case ROUTE_ROWLN: return rowln_launch(d, s);
         case ROUTE_ROWLN_TEXT: return rowln_text_launch(d, s);
         case ROUTE_GEMM3_LN: return gemm3_ln_launch(d, s);
         case ROUTE_GEMM2_AGN:
         case ROUTE_GEMM2: return gemm2_launch(d, s);
         case ROUTE_GEMM5: return gemm5_launch(d, s);
-        case ROUTE_GEMM3_V3: return gemm3_launch(d, s, 100 + 3);          // persistent grid
-        case ROUTE_GEMM3_V7: return gemm3_launch(d, s, 100 + 7);
+        case ROUTE_GEMM3_V3:
+        case ROUTE_GEMM3_V7: return gemm3_launch(d, s, route);      // persistent grid
         case ROUTE_V1_BF16: launch_mode<1>(d, s); return (int)hipGetLastError();
         case ROUTE_V1_F32: launch_mode<0>(d, s); return (int)hipGetLastError();
         default: return -2;

@@ -1,32 +1,19 @@
 // GEMM v2 (bf16 MFMA, gfx950): BM x BN x 64 tiles, 4 waves (2 x 2), both operands streamed global -> LDS.
 //
-// LDS image per stage: [rows][64 bf16] = 128 B per row, eight 16-B chunks stored XOR-swizzled
-// (slot = chunk ^ (row & 7)) so that the 16x16x32 fragment reads (16 rows x one chunk per lane group) are
-// conflict-free for ds_read_b128.  A wave instruction fills 8 rows x 128 B = 1 KiB; lane L lands at
-// base + 16 L, i.e. row L/8, slot L%8, so it fetches global chunk (L%8) ^ (L/8): the swizzle lives in the
-// per-lane SOURCE address (the LDS-DMA destination is lane-linear).
+// LDS image per stage: the swizzled [rows][64 bf16] image of gemm_tile.h.
 //   * bf16 operands (weights, and A when the activation is stored bf16): global_load_lds_dwordx4 straight
 //     into LDS; out-of-range taps / rows / k read a 16-B zero page.
 //   * fp32 A (residual streams kept in fp32): the same lane -> (row, chunk) map, loaded to registers,
 //     converted to bf16 and written with ds_write_b128 after the MFMAs of the current tile.
 // Two LDS stages: tile t+1 is issued before the MFMAs of tile t; one drain + barrier per k-tile.
-#include "common.h"
-#include "prof.h"
-#include "gemm.h"
-#include "gemm_epi.h"
+#include "gemm_launch.h"
+#include "gemm_tile.h"
 
 namespace athd {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16v8;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) void gbl_void;
-
-__device__ __attribute__((aligned(64))) uint4 g_zero_page[4];
-
 template <int BM, int BN, bool A_BF16, unsigned F>
 __global__ __launch_bounds__(256) void gemm2_kernel(const GemmDesc d) {
-    constexpr int ROWB = 128;                                  // bytes per LDS row (64 bf16)
-    constexpr int STAGE = (BM + BN) * ROWB;
+    constexpr int STAGE = (BM + BN) * LDS_ROWB;
     constexpr int TM = BM / 2 / 16, TN = BN / 2 / 16;
     constexpr int AQ = BM / 32;                                // A instructions (8 rows each) per wave
     constexpr int BQ = BN / 32;
@@ -40,17 +27,13 @@ __global__ __launch_bounds__(256) void gemm2_kernel(const GemmDesc d) {
     // column tiles of a row block run together on one XCD and read its A rows from HBM once (a 2-D grid ran every
     // row block's column tiles ntm blocks apart: the downsampler's fp32 A was read 2.2x, PMC)
     const int ntm2 = (int)(((int64_t)d.nb * d.H_out * d.W + BM - 1) / BM), ntn2 = (d.N + BN - 1) / BN;
-    int id2;
-    {
-        const int n = ntm2 * ntn2, q = n / 8, r = n % 8, x = (int)blockIdx.x % 8;
-        id2 = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (int)blockIdx.x / 8;
-    }
+    const int id2 = xcd_remap((int)blockIdx.x, ntm2 * ntn2);
     const int64_t m0 = (int64_t)(id2 / ntn2) * BM;
     const int n0 = (id2 % ntn2) * BN;
     const int64_t a_bs = d.a_bs >= 0 ? d.a_bs : (int64_t)d.H_in * d.W * d.a_ld;
     const int64_t rowpitch = d.a_hs >= 0 ? d.a_hs : (int64_t)d.W * d.a_ld;
     const int lrow = lane >> 3;                                // row within an 8-row instruction
-    const int chunk = (lane & 7) ^ lrow;                       // global 16-B chunk this lane fetches
+    const int chunk = swz_chunk(lane);                         // global 16-B chunk this lane fetches
 
     // per-lane A rows: row = 8 (wave + 4 q) + lrow
     int64_t a_base[AQ];
@@ -91,7 +74,8 @@ __global__ __launch_bounds__(256) void gemm2_kernel(const GemmDesc d) {
     if constexpr (!A_BF16) {
         if (d.a_gn_stats) {
 #pragma unroll
-            for (int q = 0; q < AQ; ++q) {
+            for (int q = 0; q < AQ; ++q) {       // (common.h's gn_params, written out: a call to it changes the machine
+                                                 //  code and register counts of the fp32-A kernels)
                 const double m = d.a_gn_stats[2 * a_b[q]] / (double)d.a_gn_count;
                 double var = d.a_gn_stats[2 * a_b[q] + 1] / (double)d.a_gn_count - m * m;
                 if (var < 0) var = 0;
@@ -103,7 +87,7 @@ __global__ __launch_bounds__(256) void gemm2_kernel(const GemmDesc d) {
 
     auto issue = [&](int kt, int st) {
         char* sA = smem + st * STAGE;
-        char* sB = sA + BM * ROWB;
+        char* sB = sA + BM * LDS_ROWB;
         const bool kok = k_cur < d.K;
         ra_ci = ci;
 #pragma unroll
@@ -113,7 +97,7 @@ __global__ __launch_bounds__(256) void gemm2_kernel(const GemmDesc d) {
             const int64_t off = a_base[q] + (int64_t)row * rowpitch + ci;
             if constexpr (A_BF16) {
                 const char* src = ok ? (const char*)d.A + off * 2 : zero;
-                __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(sA + (wave + 4 * q) * 1024), 16, 0, 0);
+                dma16(src, sA + (wave + 4 * q) * 1024);
             } else if (flat) {
                 // flat K (C_in < 8, taps contiguous): the 8 elements span taps tap .. tap + (ci + 7) / C_in
                 const int row_l = row + (ci + 7) / d.C_in * d.dil;
@@ -152,7 +136,7 @@ __global__ __launch_bounds__(256) void gemm2_kernel(const GemmDesc d) {
 #pragma unroll
         for (int q = 0; q < BQ; ++q) {
             const char* src = bptr[q] ? bptr[q] + (int64_t)kt * 128 : zero;
-            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(sB + (wave + 4 * q) * 1024), 16, 0, 0);
+            dma16(src, sB + (wave + 4 * q) * 1024);
         }
         // advance this lane's k by 64
         k_cur += 64;
@@ -207,15 +191,15 @@ __global__ __launch_bounds__(256) void gemm2_kernel(const GemmDesc d) {
         const int cur = kt & 1;
         if (kt + 1 < nk) issue(kt + 1, cur ^ 1);
         const char* sA = smem + cur * STAGE;
-        const char* sB = sA + BM * ROWB;
+        const char* sB = sA + BM * LDS_ROWB;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            const int slot = ((4 * ks + g) ^ (fr & 7)) * 16;
+            const int slot = swz_slot(ks, g, fr);
             bf16v8 af[TM], bfr[TN];
 #pragma unroll
-            for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const bf16v8*>(sA + (wm0 + 16 * i + fr) * ROWB + slot);
+            for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const bf16v8*>(sA + (wm0 + 16 * i + fr) * LDS_ROWB + slot);
 #pragma unroll
-            for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const bf16v8*>(sB + (wn0 + 16 * j + fr) * ROWB + slot);
+            for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const bf16v8*>(sB + (wn0 + 16 * j + fr) * LDS_ROWB + slot);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -248,26 +232,14 @@ template <int BM, int BN, unsigned F>
 static void launch2f(const GemmDesc& d, hipStream_t s) {
     const int64_t M = (int64_t)d.nb * d.H_out * d.W;
     dim3 grid((unsigned)(((M + BM - 1) / BM) * ((d.N + BN - 1) / BN)));
-    KScope ks(s);
-    if (ks.on()) {
-        double fl, by;
-        gemm_work(d, 1, fl, by);
-        ks.begin(klabel("gemm2_kernel<%d,%d,%s,%u>", BM, BN, d.a_bf16 ? "true" : "false", F), fl, by);
-    }
+    GemmScope ks(s, d, 1, "gemm2_kernel<%d,%d,%s,%u>", BM, BN, d.a_bf16 ? "true" : "false", F);
     if (d.a_bf16) hipLaunchKernelGGL((gemm2_kernel<BM, BN, true, F>), grid, dim3(256), 0, s, with_fastdiv(d));
     else hipLaunchKernelGGL((gemm2_kernel<BM, BN, false, F>), grid, dim3(256), 0, s, with_fastdiv(d));
 }
 
 template <int BM, int BN>
 static void launch2(const GemmDesc& d, hipStream_t s) {
-    const unsigned f = epi_flags(d);
-    switch (f) {
-#define ATHD_CASE(FL) \
-    case (FL): launch2f<BM, BN, (FL)>(d, s); return;
-        ATHD_EPI_LIST(ATHD_CASE)
-#undef ATHD_CASE
-        default: launch2f<BM, BN, F_ALL>(d, s); return;
-    }
+    dispatch_epi(epi_flags(d), [&](auto f) { launch2f<BM, BN, decltype(f)::value>(d, s); });
 }
 
 int gemm2_launch(const GemmDesc& d, hipStream_t s) {

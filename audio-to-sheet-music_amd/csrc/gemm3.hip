@@ -1,33 +1,16 @@
 // GEMM v3 (bf16 MFMA, gfx950), for bf16 activations: BM x BN x 64 tiles, WM x WN waves, a STAGES-deep LDS ring
 // filled by global_load_lds_dwordx4 with a COUNTED vmcnt and raw s_barrier, so STAGES-2 tiles stay in flight
 // across every barrier (a __syncthreads() would drain them: cdna_hip_programming.md §5 "Pipelining across
-// barriers").  LDS image and swizzle as in gemm2.hip (per-lane source chunk (L%8)^(L/8), slot = chunk ^ (row&7)).
-// Same descriptor and epilogue (C^T tiles) as the other GEMM kernels.
-#include "common.h"
-#include "prof.h"
-#include "gemm.h"
-#include "gemm_epi.h"
+// barriers").  LDS image and swizzle: gemm_tile.h.  Same descriptor and epilogue (C^T tiles) as the other GEMM
+// kernels.  The M tiles are taken in XCD order (xcd_remap): neighbouring tiles share input rows (conv taps) in that L2.
+// The product builds the two routed tile shapes and the F_TEXT_LN form (gemm3_launch / gemm3_ln_launch); the other
+// shapes of the round-by-round tile search and the one-tile-per-block grid are in the ATHD_KBENCH table at the end.
+#include "gemm_launch.h"
+#include "gemm_tile.h"
+
+#include <algorithm>
 
 namespace athd {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16v8;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) void gbl_void;
-
-static __device__ __attribute__((aligned(64))) uint4 g_zero_page3[4];
-
-template <int N>
-ATHD_DEV void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// XCD-aware tile order (cdna_hip_programming.md T1): workgroup i runs on XCD i % 8, so hand each XCD a contiguous
-// range of M tiles (bijective for any tile count) - neighbouring tiles share input rows (conv taps) in that L2.
-ATHD_DEV int xcd_remap(int i, int n) {
-    const int q = n / 8, r = n % 8, x = i % 8;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i / 8;
-}
 
 // F_LN epilogue (the text cross-attention's mlp2 + norm_out, ATHTDemucs_v2.py:47-49): BN == N, so a tile holds whole
 // output rows.  v = acc + pbias[batch] (+ bias) + residual (batch / res_div, f32), then LayerNorm over the row: the
@@ -120,8 +103,7 @@ ATHD_DEV void gemm3_epilogue_ln(const GemmDesc& d, f32x4_t (&acc)[TM][TN], int64
 template <int BM, int BN, int WM, int WN, int STAGES, unsigned F>
 __global__ __launch_bounds__(WM * WN * 64) void gemm3_kernel(const GemmDesc d) {
     constexpr int NW = WM * WN;
-    constexpr int ROWB = 128;
-    constexpr int STAGE = (BM + BN) * ROWB;
+    constexpr int STAGE = (BM + BN) * LDS_ROWB;
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
     constexpr int AQ = BM / 8 / NW, BQ = BN / 8 / NW;
     static_assert(AQ * 8 * NW == BM && BQ * 8 * NW == BN, "tile / wave count");
@@ -139,7 +121,7 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm3_kernel(const GemmDesc d) {
     const int64_t a_bs = d.a_bs >= 0 ? d.a_bs : (int64_t)d.H_in * d.W * d.a_ld;
     const int64_t rowpitch = d.a_hs >= 0 ? d.a_hs : (int64_t)d.W * d.a_ld;
     const int lrow = lane >> 3;
-    const int chunk = (lane & 7) ^ lrow;
+    const int chunk = swz_chunk(lane);
 
     // Tile loop: block x takes M tiles x, x + gridDim.x, ... (one tile when gridDim.x == ntm; persistent when the
     // launch sizes the grid to the resident blocks, gridDim.x % 8 == 0 so every tile of a block maps to its XCD's
@@ -175,24 +157,24 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm3_kernel(const GemmDesc d) {
         const int n = n0 + 8 * (wave + NW * q) + lrow;
         bptr[q] = n < d.N ? (const char*)d.Wp + ((int64_t)n * d.Kp + 8 * chunk) * 2 : nullptr;
     }
-    const char* zero = reinterpret_cast<const char*>(g_zero_page3);
+    const char* zero = reinterpret_cast<const char*>(g_zero_page);
     const int nk = d.Kp / 64;
 
     auto issue = [&](int kt, int st) {
         char* sA = smem + st * STAGE;
-        char* sB = sA + BM * ROWB;
+        char* sB = sA + BM * LDS_ROWB;
         const bool kok = k_cur < d.K;
 #pragma unroll
         for (int q = 0; q < AQ; ++q) {
             const int row = a_h0[q] + tap * d.dil;
             const bool ok = a_ok[q] && kok && row >= 0 && row < d.H_in;
             const char* src = ok ? (const char*)d.A + (a_base[q] + (int64_t)row * rowpitch + ci) * 2 : zero;
-            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(sA + (wave + NW * q) * 1024), 16, 0, 0);
+            dma16(src, sA + (wave + NW * q) * 1024);
         }
 #pragma unroll
         for (int q = 0; q < BQ; ++q) {
             const char* src = bptr[q] ? bptr[q] + (int64_t)kt * 128 : zero;
-            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(sB + (wave + NW * q) * 1024), 16, 0, 0);
+            dma16(src, sB + (wave + NW * q) * 1024);
         }
         k_cur += 64;
         ci += 64;
@@ -232,16 +214,16 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm3_kernel(const GemmDesc d) {
             const int nxt = kt + STAGES - 1;
             if (nxt < nk) issue(nxt, nxt % STAGES);
             const char* sA = smem + cur * STAGE;
-            const char* sB = sA + BM * ROWB;
+            const char* sB = sA + BM * LDS_ROWB;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 if (2 * kt + ks < s_lo || 2 * kt + ks >= s_hi) continue;
-                const int slot = ((4 * ks + g) ^ (fr & 7)) * 16;
+                const int slot = swz_slot(ks, g, fr);
                 bf16v8 af[TM], bfr[TN];
 #pragma unroll
-                for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const bf16v8*>(sA + (wm0 + 16 * i + fr) * ROWB + slot);
+                for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const bf16v8*>(sA + (wm0 + 16 * i + fr) * LDS_ROWB + slot);
 #pragma unroll
-                for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const bf16v8*>(sB + (wn0 + 16 * j + fr) * ROWB + slot);
+                for (int j = 0; j < TN; ++j) bfr[j] = *reinterpret_cast<const bf16v8*>(sB + (wn0 + 16 * j + fr) * LDS_ROWB + slot);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -292,54 +274,28 @@ bool gemm3_supported(const GemmDesc& d) {
            (d.act != ACT_GLU || d.N % 32 == 0);
 }
 
-// Persistent grid: resident blocks per CU (occupancy API, once per instantiation) x CUs, split over the N tiles,
-// rounded down to a multiple of 8 (XCD count) and capped at the M tile count.
-template <int BM, int BN, int WM, int WN, int ST, unsigned F>
-static unsigned resident_grid_x(int ntm, int ntn) {
-    static int per_cu = 0;       // a property of the kernel; the CU count is the current device's
-    if (per_cu == 0) {
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm3_kernel<BM, BN, WM, WN, ST, F>, WM * WN * 64, 0);
-        if (per_cu <= 0) per_cu = -1;
-    }
-    const int resident = per_cu > 0 ? per_cu * device_cus() : -1;
-    if (resident < 0) return (unsigned)ntm;
-    int gx = resident / ntn / 8 * 8;
-    if (gx < 8) gx = 8;
-    return (unsigned)(gx < ntm ? gx : ntm);
-}
-
+// Persistent grid: the resident blocks (resident_blocks) split over the N tiles, rounded down to a multiple of 8
+// (XCD count) and capped at the M tile count; unknown residency or !persist: one block per M tile.
 template <int BM, int BN, int WM, int WN, int ST, unsigned F>
 static void launch3f(const GemmDesc& d, hipStream_t s, bool persist) {
     const int64_t M = (int64_t)d.nb * d.H_out * d.W;
     const int ntm = (int)((M + BM - 1) / BM), ntn = (d.N + BN - 1) / BN;
-    dim3 grid(persist ? resident_grid_x<BM, BN, WM, WN, ST, F>(ntm, ntn) : (unsigned)ntm, (unsigned)ntn);
-    KScope ks(s);
-    if (ks.on()) {
-        double fl, by;
-        gemm_work(d, 1, fl, by);
-        ks.begin(klabel("gemm3_kernel<%d,%d,%d,%d,%d,%u>", BM, BN, WM, WN, ST, F), fl, by);
-    }
-    hipLaunchKernelGGL((gemm3_kernel<BM, BN, WM, WN, ST, F>), grid, dim3(WM * WN * 64), 0, s, with_fastdiv(d));
+    const int64_t resident = persist ? resident_blocks<gemm3_kernel<BM, BN, WM, WN, ST, F>>(WM * WN * 64) : 0;
+    int gx = ntm;
+    if (resident > 0) gx = std::min(ntm, std::max(8, (int)(resident / ntn / 8 * 8)));
+    GemmScope ks(s, d, 1, "gemm3_kernel<%d,%d,%d,%d,%d,%u>", BM, BN, WM, WN, ST, F);
+    hipLaunchKernelGGL((gemm3_kernel<BM, BN, WM, WN, ST, F>), dim3((unsigned)gx, (unsigned)ntn), dim3(WM * WN * 64), 0, s,
+                       with_fastdiv(d));
 }
 
 template <int BM, int BN, int WM, int WN, int ST>
 static void launch3(const GemmDesc& d, hipStream_t s, bool persist) {
-    switch (epi_flags(d)) {
-#define ATHD_CASE(FL) \
-    case (FL): launch3f<BM, BN, WM, WN, ST, (FL)>(d, s, persist); return;
-        ATHD_EPI_LIST(ATHD_CASE)
-#undef ATHD_CASE
-        default: launch3f<BM, BN, WM, WN, ST, F_ALL>(d, s, persist); return;
-    }
+    dispatch_epi(epi_flags(d), [&](auto f) { launch3f<BM, BN, WM, WN, ST, decltype(f)::value>(d, s, persist); });
 }
 
 // the row-LayerNorm epilogue exists only here (gemm3_ln_launch): BN == N
 static constexpr unsigned F_TEXT_LN = F_RES | F_PB | F_LN | F_CBF16;
 
-// variant: 0 = auto, 1 = 256x128 (8 waves, 3 stages), 2 = 128x128 (4 waves, 3 stages), 3 = 256x192 (8 waves, 2 st),
-// 4 = 128x192 (4 waves, 2 stages: 80 KB LDS, 2 blocks/CU), 5 = 128x192 (4 waves, 3 stages), 6 = 128x96 (4 waves, 3 st),
-// 7 = 192x192 (8 waves, 3 stages: 144 KB LDS), 8 = 128x192 (8 waves, 2 stages: 80 KB, 2 blocks/CU); + 100: persistent
-// grid (resident blocks walk the M tiles)
 bool gemm3_ln_supported(const GemmDesc& d) {
     return !(epi_flags(d) != F_TEXT_LN || d.N != 384 || !gemm3_supported(d) || d.ldo != 384 || d.res_bf16 || d.col_off != 0);
 }
@@ -350,7 +306,20 @@ int gemm3_ln_launch(const GemmDesc& d, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-int gemm3_launch(const GemmDesc& d, hipStream_t s, int variant) {
+// the routed tile shapes, both 8 waves on a persistent grid: 192 x 192 with 3 stages (144 KB LDS), else 256 x 192 with 2
+int gemm3_launch(const GemmDesc& d, hipStream_t s, GemmRoute route) {
+    if (route == ROUTE_GEMM3_V7) launch3<192, 192, 4, 2, 3>(d, s, true);
+    else launch3<256, 192, 4, 2, 2>(d, s, true);
+    return (int)hipGetLastError();
+}
+
+#ifdef ATHD_KBENCH
+// The tile-shape table of tools/kbench (variants 3 and 7 are the product's):
+// variant: 0 = auto, 1 = 256x128 (8 waves, 3 stages), 2 = 128x128 (4 waves, 3 stages), 3 = 256x192 (8 waves, 2 st),
+// 4 = 128x192 (4 waves, 2 stages: 80 KB LDS, 2 blocks/CU), 5 = 128x192 (4 waves, 3 stages), 6 = 128x96 (4 waves, 3 st),
+// 7 = 192x192 (8 waves, 3 stages: 144 KB LDS), 8 = 128x192 (8 waves, 2 stages: 80 KB, 2 blocks/CU); + 100: persistent
+// grid (resident blocks walk the M tiles)
+int gemm3_variant_launch(const GemmDesc& d, hipStream_t s, int variant) {
     const bool persist = variant >= 100;
     if (persist) variant -= 100;
     if (variant == 0) variant = (d.N % 192 == 0 && d.N % 128 != 0) ? 3 : 1;
@@ -364,5 +333,6 @@ int gemm3_launch(const GemmDesc& d, hipStream_t s, int variant) {
     else launch3<256, 192, 4, 2, 2>(d, s, persist);
     return (int)hipGetLastError();
 }
+#endif
 
 }  // namespace athd

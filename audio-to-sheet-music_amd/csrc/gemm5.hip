@@ -23,22 +23,15 @@
 // of its time in isolation, so gemm5 has none.
 // Persistent grid (epilogues without residual or statistics, as gemm4): the resident blocks walk their tiles and
 // issue the next tile's first K-tiles before the current tile's epilogue.
-#include "common.h"
-#include "prof.h"
-#include "gemm.h"
-#include "gemm_epi.h"
+#include "gemm_launch.h"
+#include "gemm_tile.h"
 
 #include <algorithm>
 #include <climits>
-#include <type_traits>
 
 namespace athd {
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16v8;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) void gbl_void;
 
 constexpr int G5_SLOT = 16384;     // one half-tile slot: 128 rows x 64 bf16
 // The K-loop's VM-counter bookkeeping: every issueA / issueB issues exactly G5_PIECES LDS-DMA pieces,
@@ -74,14 +67,7 @@ ATHD_HD constexpr bool g5_persist(unsigned F) {
     return (F & (F_RES | F_STATS)) == 0 || (ATHD_G5_PRES && (F & F_RGN) == 0 && (F & ~(F_RES | F_STATS)) == 0);
 }
 
-ATHD_DEV int xcd_remap5(int i, int n) {
-    const int q = n / 8, r = n % 8, x = i % 8;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i / 8;
-}
-
 }  // namespace
-
-__device__ __attribute__((aligned(64))) uint4 g_zero_page5[4];
 
 // PROBE (tools/kbench ablations only; the product instantiates 0): 1 = no LDS-DMA staging in the K-loop, 2 = no
 // fragment reads in the K-loop, 3 = no MFMAs, 4 = no section barriers in the K-loop (results are garbage).
@@ -112,8 +98,8 @@ __global__ __launch_bounds__(512) void gemm5_kernel(const GemmDesc d) {
     const int64_t a_bs = d.a_bs >= 0 ? d.a_bs : (int64_t)d.H_in * d.W * d.a_ld;
     const int64_t rowpitch = d.a_hs >= 0 ? d.a_hs : (int64_t)d.W * d.a_ld;
     const int lrow = lane >> 3;
-    const int chunk = (lane & 7) ^ lrow;       // global 16-B chunk this lane fetches (LDS slot = chunk ^ row&7)
-    const char* zero = reinterpret_cast<const char*>(g_zero_page5);
+    const int chunk = swz_chunk(lane);         // global 16-B chunk this lane fetches (gemm_tile.h)
+    const char* zero = reinterpret_cast<const char*>(g_zero_page);
 
     int tile = blockIdx.x;
     int64_t m0 = 0;
@@ -136,7 +122,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(const GemmDesc d) {
             nk = (p + 1) * nkt / d.sk_S - kb0;
             sk_piece = q;
         } else {
-            id = xcd_remap5(t, !PERSIST && d.sk_ws ? d.sk_full : ntiles);
+            id = xcd_remap(t, !PERSIST && d.sk_ws ? d.sk_full : ntiles);
         }
         m0 = (int64_t)(id / ntn) * 256;
         n0 = (id % ntn) * 256;
@@ -171,6 +157,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(const GemmDesc d) {
         if constexpr (LIN) {
             const char* base = (const char*)d.A + (int64_t)(kb0 + kt) * 128;      // wave-uniform
 #pragma unroll
+            // (the builtin itself: through dma16 hipcc schedules this form's address adds in another order)
             for (int q = 0; q < G5_PIECES; ++q)
                 __builtin_amdgcn_global_load_lds((gbl_void*)(base + a_base[h][q]), (lds_void*)(dst + (wave + NW * q) * 1024),
                                                  16, 0, 0);
@@ -184,7 +171,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(const GemmDesc d) {
             const int row = a_h0[h][q] + tap * d.dil;
             const bool ok = kok && row >= 0 && row < d.H_in;
             const char* src = ok ? (const char*)d.A + ((int64_t)a_base[h][q] + (int64_t)row * rowpitch + ci) * 2 : zero;
-            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(dst + (wave + NW * q) * 1024), 16, 0, 0);
+            dma16(src, dst + (wave + NW * q) * 1024);
         }
     };
     auto issueB = [&](int kt, int h) {
@@ -192,8 +179,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(const GemmDesc d) {
         char* dst = smem + ((kt & 1) * 4 + 2 + h) * G5_SLOT;
         const char* wb = (const char*)d.Wp + (int64_t)(kb0 + kt) * 128 + (h ? b_h1 : 0u);
 #pragma unroll
-        for (int q = 0; q < G5_PIECES; ++q)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(wb + b_off[q]), (lds_void*)(dst + (wave + NW * q) * 1024), 16, 0, 0);
+        for (int q = 0; q < G5_PIECES; ++q) dma16(wb + b_off[q], dst + (wave + NW * q) * 1024);
     };
 
     const int fr = lane & 15, g = lane >> 4;
@@ -204,7 +190,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(const GemmDesc d) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                af[i][ks] = *reinterpret_cast<const bf16v8*>(base + i * 16 * 128 + ((4 * ks + g) ^ (fr & 7)) * 16);
+                af[i][ks] = *reinterpret_cast<const bf16v8*>(base + i * 16 * 128 + swz_slot(ks, g, fr));
     };
     auto readB = [&](int buf, int nh, bf16v8 (&bf)[2][2]) {
         if (PROBE == 2) return;
@@ -213,7 +199,7 @@ __global__ __launch_bounds__(512) void gemm5_kernel(const GemmDesc d) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                bf[j][ks] = *reinterpret_cast<const bf16v8*>(base + j * 16 * 128 + ((4 * ks + g) ^ (fr & 7)) * 16);
+                bf[j][ks] = *reinterpret_cast<const bf16v8*>(base + j * 16 * 128 + swz_slot(ks, g, fr));
     };
 
     f32x4_t acc[TM][TN];
@@ -504,17 +490,6 @@ static constexpr bool sk_form() {
     return !g5_persist(F) && LIN && (F == (F_RES | F_STATS) || F == F_RES);
 }
 
-// resident blocks of one round of gemm5_kernel<F, PROBE, LIN> on the current device (0: unknown)
-template <unsigned F, int PROBE, bool LIN>
-static int64_t sk_resident() {
-    static int per_cu = 0;   // a property of the kernel; the CU count is the current device's
-    if (per_cu == 0) {
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm5_kernel<F, PROBE, LIN>, 512, 0);
-        if (per_cu <= 0) per_cu = -1;
-    }
-    return per_cu > 0 ? (int64_t)per_cu * device_cus() : 0;
-}
-
 // Split-K tail: a grid of `tiles` one-tile blocks at R resident blocks runs ceil(tiles / R) rounds; the last
 // round's `tail` tiles (e.g. linear2: 1036 = 4 x 256 + 12) leave the other CUs idle for a whole tile time.
 // Those tiles are cut into S K pieces each (>= 4 K-tiles), computed as extra blocks of the same launch, and
@@ -545,18 +520,13 @@ static void launch5f(const GemmDesc& d, hipStream_t s) {
     const int64_t tiles = ((M + 255) / 256) * ((d.N + 255) / 256);
     int64_t grid = tiles;
     if constexpr (g5_persist(F)) {   // persistent: the resident blocks (one per CU), a multiple of 8
-        static int per_cu = 0;   // a property of the kernel; the CU count is the current device's
-        if (per_cu == 0) {
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm5_kernel<F, PROBE, LIN>, 512, 0);
-            if (per_cu <= 0) per_cu = -1;
-        }
-        const int resident = per_cu > 0 ? per_cu * device_cus() / 8 * 8 : -1;
+        const int64_t resident = resident_blocks<gemm5_kernel<F, PROBE, LIN>>(512) / 8 * 8;
         if (resident >= 8 && resident < tiles) grid = resident;
     }
     GemmDesc e = with_fastdiv(d);
     int sk_tail = 0;
     if constexpr (sk_form<F, LIN>()) {
-        const SkPlan p = gemm5_sk_plan(d, sk_resident<F, PROBE, LIN>());
+        const SkPlan p = gemm5_sk_plan(d, resident_blocks<gemm5_kernel<F, PROBE, LIN>>(512));
         if (p.S >= 2) {
             e.sk_full = p.full;
             e.sk_S = p.S;
@@ -566,12 +536,7 @@ static void launch5f(const GemmDesc& d, hipStream_t s) {
     }
     if (!sk_tail) e.sk_ws = nullptr;
     {
-        KScope ks(s);
-        if (ks.on()) {
-            double fl, by;
-            gemm_work(d, 1, fl, by);
-            ks.begin(klabel("gemm5_kernel<%u,%d,%s>", F, PROBE, LIN ? "true" : "false"), fl, by);
-        }
+        GemmScope ks(s, d, 1, "gemm5_kernel<%u,%d,%s>", F, PROBE, LIN ? "true" : "false");
         hipLaunchKernelGGL((gemm5_kernel<F, PROBE, LIN>), dim3((unsigned)grid), dim3(512), 0, s, e);
     }
     if (sk_tail) {
@@ -595,20 +560,21 @@ static bool gemm5_lin(const GemmDesc& d) {
 int64_t gemm5_sk_resident(const GemmDesc& d) {
     if (!(ATHD_G5_LIN && gemm5_lin(d))) return 0;
     const unsigned f = epi_flags(d);
-    if (f == (F_RES | F_STATS)) return sk_form<F_RES | F_STATS, true>() ? sk_resident<F_RES | F_STATS, 0, true>() : 0;
-    if (f == F_RES) return sk_form<F_RES, true>() ? sk_resident<F_RES, 0, true>() : 0;
+    constexpr unsigned RS = F_RES | F_STATS;
+    if (f == RS && sk_form<RS, true>()) return resident_blocks<gemm5_kernel<RS, 0, true>>(512);
+    if (f == F_RES && sk_form<F_RES, true>()) return resident_blocks<gemm5_kernel<F_RES, 0, true>>(512);
     return 0;
 }
 
 int gemm5_launch(const GemmDesc& d, hipStream_t s) {
     const bool lin = ATHD_G5_LIN && gemm5_lin(d);
-    switch (epi_flags(d)) {
-#define ATHD_CASE(FL) \
-    case (FL): lin ? launch5f<(FL), 0, true>(d, s) : launch5f<(FL)>(d, s); break;
-        ATHD_EPI_LIST(ATHD_CASE)
-#undef ATHD_CASE
-        default: launch5f<F_ALL>(d, s); break;
-    }
+    dispatch_epi(epi_flags(d), [&](auto f) {
+        constexpr unsigned F = decltype(f)::value;
+        if constexpr (F != F_ALL) {     // (the general epilogue form exists in the implicit-GEMM addressing only)
+            if (lin) return launch5f<F, 0, true>(d, s);
+        }
+        launch5f<F>(d, s);
+    });
     return (int)hipGetLastError();
 }
 

@@ -16,10 +16,8 @@
 //     fragments are issued before the current tile's epilogue (gemm_epi.h), so their latency hides under it.
 #include <cstdlib>
 
-#include "common.h"
-#include "prof.h"
-#include "gemm.h"
-#include "gemm_epi.h"
+#include "gemm_launch.h"
+#include "gemm_tile.h"
 
 namespace athd {
 
@@ -30,13 +28,6 @@ constexpr int G6_TM = G6_BM / 16, G6_TN = G6_BN / G6_NW / 16;     // 16 x 2 tile
 constexpr int G6_STAGE = G6_BM * 128;                           // 32 KB: 256 rows x 64 bf16
 constexpr int G6_NS = 4;                                        // A ring depth
 constexpr int G6_AQ = G6_BM / 8 / G6_NW;                        // A DMA pieces per wave per K-tile (4)
-typedef __attribute__((address_space(3))) void g6_lds_void;
-typedef __attribute__((address_space(1))) void g6_gbl_void;
-
-ATHD_DEV int g6_xcd_remap(int i, int n) {
-    const int q = n / 8, r = n % 8, x = i % 8;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i / 8;
-}
 
 }  // namespace
 
@@ -56,7 +47,7 @@ __global__ __launch_bounds__(G6_NT, 2) void gemm6_kernel(const GemmDesc d) {
     const int KT = d.K / 64;
     const int wn0 = 32 * wave;
     const uint32_t a_lds = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) char*)ring;
-    const int lrow = lane >> 3, chunk = (lane & 7) ^ lrow;
+    const int lrow = lane >> 3, chunk = swz_chunk(lane);
 
     // tiles in (m tile, n tile) order, each XCD a contiguous range: the n tiles of an m tile share its A rows in L2
     int tile = (int)blockIdx.x;
@@ -70,7 +61,7 @@ __global__ __launch_bounds__(G6_NT, 2) void gemm6_kernel(const GemmDesc d) {
     const char* const abase = (const char*)d.A;
     const uint32_t boff = (uint32_t)(l15 * d.Kp + 8 * l4) * 2;
     auto setup = [&](int t) {
-        const int L = g6_xcd_remap(t, ntiles);
+        const int L = xcd_remap(t, ntiles);
         m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)((L / ntn) * G6_BM));
         n0 = __builtin_amdgcn_readfirstlane((L % ntn) * G6_BN);
 #pragma unroll
@@ -89,8 +80,7 @@ __global__ __launch_bounds__(G6_NT, 2) void gemm6_kernel(const GemmDesc d) {
         const char* ab = abase + (int64_t)(real ? kt : 0) * 128;
 #pragma unroll
         for (int q = 0; q < G6_AQ; ++q)
-            __builtin_amdgcn_global_load_lds((g6_gbl_void*)(ab + aoff[q]),
-                                             (g6_lds_void*)(real ? dst + (wave + G6_NW * q) * 1024 : dst), 16, 0, 0);
+            dma16(ab + aoff[q], real ? dst + (wave + G6_NW * q) * 1024 : dst);
     };
     // B fragments G6_BD K-steps ahead in a ring of G6_BD + 1 register sets: the A DMA of K-tile kt + 3, issued
     // after B(2 kt + 3), then stays in flight until the wait for B(2 kt + 4), two K-tiles later (one vmcnt orders both
@@ -152,7 +142,7 @@ __global__ __launch_bounds__(G6_NT, 2) void gemm6_kernel(const GemmDesc d) {
             G6_WAIT_B(ks, BUF);                                                                                    \
             if (ks == 0) __builtin_amdgcn_s_barrier();    /* A(0) of every wave */                                \
             const uint32_t ab = a_lds + (uint32_t)((kt % G6_NS) * G6_STAGE) + (uint32_t)(l15 * 128) +             \
-                                (uint32_t)(((4 * s + l4) ^ (l15 & 7)) * 16);                                       \
+                                (uint32_t)swz_slot(s, l4, l15);                                                    \
             /* the 16 row fragments in 4 groups of 4, the next group's reads in flight over the MFMAs */           \
             bf16x8_t af[2][4];                                                                                     \
             for (int u = 0; u < 4; ++u)                                                                            \
@@ -238,12 +228,7 @@ static void launch6f(const GemmDesc& d, hipStream_t s) {
     int64_t grid = (int64_t)device_cus() / 8 * 8;            // one 128-KB-LDS workgroup per CU, whole XCD rounds
     if (grid < 8) grid = 8;
     if (grid > tiles) grid = tiles;
-    KScope ks(s);
-    if (ks.on()) {
-        double fl, by;
-        gemm_work(d, 1, fl, by);
-        ks.begin(klabel("gemm6_kernel<%u>", F), fl, by);
-    }
+    GemmScope ks(s, d, 1, "gemm6_kernel<%u>", F);
     hipLaunchKernelGGL((gemm6_kernel<F>), dim3((unsigned)grid), dim3(G6_NT), 0, s, with_fastdiv(d));
 }
 

@@ -26,9 +26,8 @@
 //     X stored, the row's sum and then its squared deviations reduced across the 8 waves in LDS (layernorm_kernel's
 //     two-pass form), H stored as bf16.  Per-column parameters (bias, scale, GroupNorm and LayerNorm affines) come
 //     from LDS: 16 columns x 6 parameters in registers would not fit beside the 128 accumulators.
-#include "common.h"
-#include "prof.h"
-#include "gemm.h"
+#include "gemm_launch.h"
+#include "gemm_tile.h"
 
 namespace athd {
 
@@ -37,15 +36,6 @@ namespace {
 constexpr int RL_N = 512, RL_K = 512;           // the out_proj shape
 constexpr int RT_N = 384, RT_K = 384;           // the text cross-attention's mlp2 shape (TEXT)
 constexpr int RL_NS = 3;                         // A ring depth
-typedef __attribute__((address_space(3))) void rl_lds_void;
-typedef __attribute__((address_space(1))) void rl_gbl_void;
-__device__ __attribute__((aligned(64))) uint4 g_zero_rl[4];
-
-template <int N>
-ATHD_DEV void rl_wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // The VM issue schedule of the K-loop, for the counted waits (every count is the number of VM operations issued AFTER
 // the one waited for).  Prologue: B(0) (TN loads), A(0), A(1) (AQ DMAs each).  K-step ks: B(ks + 1), then at even ks
 // A(ks / 2 + 2).
@@ -107,12 +97,7 @@ __global__ __launch_bounds__(64 * NW, 2) void rowln_kernel(const GemmDesc d) {
     const uint32_t M = (uint32_t)d.nb * d.H_out;
     const uint32_t rpb = (uint32_t)d.H_out;      // rows per batch (item)
     const int ntm = (int)((M + BM - 1) / BM);
-    // XCD-aware: workgroup i runs on XCD i % 8; each XCD takes a contiguous range of row tiles
-    int tile;
-    {
-        const int n = (int)gridDim.x, q = n / 8, r = n % 8, x = (int)blockIdx.x % 8;
-        tile = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (int)blockIdx.x / 8;
-    }
+    const int tile = xcd_remap((int)blockIdx.x, (int)gridDim.x);     // each XCD a contiguous range of row tiles
     if (tile >= ntm) return;
     // (TEXT, measured: per-item tiles with the res_div prompts of a segment's rows adjacent, so that one XCD's L2
     // serves the shared residual rows: the kernel 0.49 -> 0.47 ms, the whole step 1.9 % slower, 3 alternating pairs)
@@ -137,8 +122,8 @@ __global__ __launch_bounds__(64 * NW, 2) void rowln_kernel(const GemmDesc d) {
     }
 
     // ---- operand streams ----
-    const int lrow = lane >> 3, chunk = (lane & 7) ^ lrow;
-    const char* zero = reinterpret_cast<const char*>(g_zero_rl);
+    const int lrow = lane >> 3, chunk = swz_chunk(lane);
+    const char* zero = reinterpret_cast<const char*>(g_zero_page);
     const char* arow[AQ];
 #pragma unroll
     for (int q = 0; q < AQ; ++q) {
@@ -152,7 +137,7 @@ __global__ __launch_bounds__(64 * NW, 2) void rowln_kernel(const GemmDesc d) {
             const char* src = arow[q] ? arow[q] + kt * 128 : zero;
             char* to = dst + (wave + NW * q) * 1024;
             if (AQ * NW > AP && wave + NW * q >= AP) to = sink;      // (wave-uniform)
-            __builtin_amdgcn_global_load_lds((rl_gbl_void*)src, (rl_lds_void*)to, 16, 0, 0);
+            dma16(src, to);
         }
     };
     // B fragments by global_load_dwordx4 in inline asm, waited for by explicit counts: with VGPR-returning loads and
@@ -178,7 +163,7 @@ __global__ __launch_bounds__(64 * NW, 2) void rowln_kernel(const GemmDesc d) {
     asm volatile("" ::: "memory");
     dma_a(0);
     dma_a(1);
-    rl_wait_vm<AQ>();                            // B(0), A(0) landed
+    wait_vm<AQ>();                               // B(0), A(0) landed
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     // K-step ks (the body is a macro so that ks is a literal in every copy: the wait counts and LDS offsets fold)
@@ -189,12 +174,12 @@ __global__ __launch_bounds__(64 * NW, 2) void rowln_kernel(const GemmDesc d) {
         asm volatile("" ::: "memory");                                                                             \
         if constexpr (s == 0 && kt + 2 < RL_KT) dma_a(kt + 2);                                                     \
         asm volatile("" ::: "memory");                                                                             \
-        rl_wait_vm<S::wait_b(ks)>();             /* B(ks) landed */                                                \
+        wait_vm<S::wait_b(ks)>();                /* B(ks) landed */                                                \
         for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(bq[(ks) & 1][j]));                                   \
         /* the A fragments by ds_read in inline asm: read through a pointer, the compiler cannot separate the ring */ \
         /* slot being read from the slots the DMAs in flight write, and puts a vmcnt(0) before the reads.  The    */ \
         /* counted wait at the end of the previous K-tile covers the slot.                                         */ \
-        const uint32_t ab = a_lds + (uint32_t)(l15 * 128 + ((4 * s + l4) ^ (l15 & 7)) * 16);                     \
+        const uint32_t ab = a_lds + (uint32_t)(l15 * 128 + swz_slot(s, l4, l15));                                 \
         bf16x8_t af[TM];                                                                                           \
         for (int i = 0; i < TM; ++i)                                                                               \
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(af[i]) : "v"(ab), "i"((kt % RL_NS) * STAGE + i * 2048)); \
@@ -205,7 +190,7 @@ __global__ __launch_bounds__(64 * NW, 2) void rowln_kernel(const GemmDesc d) {
                 if constexpr (ATHD_RL_PROBE != 2)                                                                  \
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bq[(ks) & 1][j], af[i], acc[i][j], 0, 0, 0);   \
         if constexpr (s == 1 && kt + 1 < RL_KT) {                                                                  \
-            rl_wait_vm<S::wait_a(ks)>();         /* A(kt + 1) landed (this wave's pieces) ...                  */  \
+            wait_vm<S::wait_a(ks)>();            /* A(kt + 1) landed (this wave's pieces) ...                  */  \
             __builtin_amdgcn_s_barrier();        /* ... and every wave's; slot kt % 3 is free for A(kt + 3)     */  \
         }                                                                                                          \
     }
@@ -216,7 +201,7 @@ __global__ __launch_bounds__(64 * NW, 2) void rowln_kernel(const GemmDesc d) {
     }
 #undef RL_KSTEP
 #undef load_b
-    rl_wait_vm<0>();                             // (nothing the compiler does not know of stays in flight)
+    wait_vm<0>();                                // (nothing the compiler does not know of stays in flight)
     if constexpr (ATHD_RL_PROBE == 1) {          // keep the accumulators live, store nothing
         float t = 0.f;
 #pragma unroll
@@ -429,12 +414,7 @@ int rowln_text_launch(const GemmDesc& d, hipStream_t s) {
     if (!rowln_text_supported(d)) return -2;
     const int64_t M = (int64_t)d.nb * d.H_out;
     const int ntm = (int)((M + RL_BM - 1) / RL_BM);
-    KScope ks(s);
-    if (ks.on()) {
-        double fl, by;
-        gemm_work(d, 1, fl, by);
-        ks.begin("rowln_kernel<text>", fl, by);
-    }
+    GemmScope ks(s, d, 1, "rowln_kernel<text>");
     hipLaunchKernelGGL((rowln_kernel<RL_BM, RL_NW, RT_N, RT_K, true>), dim3((unsigned)ntm), dim3(64 * RL_NW), 0, s, d);
     return (int)hipGetLastError();
 }

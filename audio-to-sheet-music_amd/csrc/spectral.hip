@@ -181,14 +181,9 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ wav
     // 1-D grid over (b, t), each XCD a contiguous range (workgroup i runs on XCD i % 8): the 4 frames that share each
     // hop of samples run on one XCD and read them from HBM once (a frame-fastest 2-D grid put neighbouring frames on
     // different XCDs: 1.6x the waveform bytes, PMC)
-    int t;
-    int64_t b;
-    {
-        const int n = (int)gridDim.x, q = n / 8, r = n % 8, x = (int)blockIdx.x % 8;
-        const int id = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (int)blockIdx.x / 8;
-        t = id % Tspec;
-        b = id / Tspec;
-    }
+    const int id = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+    const int t = id % Tspec;
+    const int64_t b = id / Tspec;
     const float* xl = wav + b * 2 * T;
     const float* xr = xl + T;
     const int64_t p0 = (int64_t)t * HOP;     // kept frame t = stft frame t+2, starts at 1024 t in the pad1d'ed signal

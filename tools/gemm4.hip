@@ -14,8 +14,6 @@
 // accumulators + 64 fragment registers + compact 32-bit addressing, no spills.
 // Same descriptor, implicit-conv A addressing and epilogue (C^T tiles, gemm_epi.h) as the other GEMM kernels.
 #include "../audio-to-sheet-music_amd/csrc/common.h"
-#include "../audio-to-sheet-music_amd/csrc/prof.h"
-#include "../audio-to-sheet-music_amd/csrc/gemm.h"
 #ifdef ATHD_G4_STAMP
 namespace athd {
 __device__ uint64_t* g4_stamp = nullptr;
@@ -27,7 +25,8 @@ constexpr int G4_NSTAMP = 24;
             athd::g4_stamp[(int64_t)blockIdx.x * athd::G4_NSTAMP + (i)] = __builtin_amdgcn_s_memtime();        \
     } while (0)
 #endif
-#include "../audio-to-sheet-music_amd/csrc/gemm_epi.h"
+#include "../audio-to-sheet-music_amd/csrc/gemm_launch.h"
+#include "../audio-to-sheet-music_amd/csrc/gemm_tile.h"
 
 #include <climits>
 #include <cstdlib>
@@ -36,17 +35,7 @@ namespace athd {
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16v8;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) void gbl_void;
-
 constexpr int G4_SLOT = 16384;     // one half-tile slot: 128 rows x 64 bf16
-
-template <int N>
-ATHD_DEV void vm_wait() {
-    static_assert(N >= 0 && N < 64, "vmcnt");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // all of this wave's LDS reads retired, then the workgroup barrier (no vmcnt: LDS-DMA stays in flight)
 ATHD_DEV void phase_barrier() {
@@ -55,14 +44,8 @@ ATHD_DEV void phase_barrier() {
     asm volatile("" ::: "memory");
 }
 
-ATHD_DEV int xcd_remap4(int i, int n) {
-    const int q = n / 8, r = n % 8, x = i % 8;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i / 8;
-}
-
 }  // namespace
 
-__device__ __attribute__((aligned(64))) uint4 g_zero_page4[4];
 // ATHD_G4_STAMP (tools/kbench build only): wave 0 lane 0 of each block records s_memtime at the phase points
 // (kernel start, prologue issued, phase 0 of K-tiles 0, 1 and the last, epilogue start / end) into g4_stamp.
 
@@ -109,8 +92,8 @@ __global__ __launch_bounds__(512) void gemm4_kernel(const GemmDesc d) {
     const int64_t a_bs = d.a_bs >= 0 ? d.a_bs : (int64_t)d.H_in * d.W * d.a_ld;
     const int64_t rowpitch = d.a_hs >= 0 ? d.a_hs : (int64_t)d.W * d.a_ld;
     const int lrow = lane >> 3;
-    const int chunk = (lane & 7) ^ lrow;       // global 16-B chunk this lane fetches (LDS slot = chunk ^ row&7)
-    const char* zero = reinterpret_cast<const char*>(g_zero_page4);
+    const int chunk = swz_chunk(lane);         // global 16-B chunk this lane fetches (gemm_tile.h)
+    const char* zero = reinterpret_cast<const char*>(g_zero_page);
 
     // this lane's slot rows: sr = 8 (wave + 8 q) + lrow, q = 0, 1 (both slot halves h use the same sr).
     // 32-bit element offsets (gemm4_supported: A < 2^31 elements; the weights hold whole 256-row tiles); a row past M
@@ -122,7 +105,7 @@ __global__ __launch_bounds__(512) void gemm4_kernel(const GemmDesc d) {
     int a_h0[2][2];
     uint32_t b_off[2];
     auto setup = [&](int t) {
-        const int id = xcd_remap4(t, ntiles);
+        const int id = xcd_remap(t, ntiles);
         m0 = (int64_t)(id / ntn) * 256;
         n0 = (id % ntn) * 256;
 #pragma unroll
@@ -156,15 +139,14 @@ __global__ __launch_bounds__(512) void gemm4_kernel(const GemmDesc d) {
             const int row = a_h0[h][q] + tap * d.dil;
             const bool ok = kok && row >= 0 && row < d.H_in;
             const char* src = ok ? (const char*)d.A + ((int64_t)a_base[h][q] + (int64_t)row * rowpitch + ci) * 2 : zero;
-            __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(dst + (wave + NW * q) * 1024), 16, 0, 0);
+            dma16(src, dst + (wave + NW * q) * 1024);
         }
     };
     auto issueB = [&](int kt, int h) {
         char* dst = smem + ((kt & 1) * 4 + 2 + h) * G4_SLOT;
         const char* wb = (const char*)d.Wp + (int64_t)kt * 128 + (h ? b_h1 : 0u);
 #pragma unroll
-        for (int q = 0; q < 2; ++q)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(wb + b_off[q]), (lds_void*)(dst + (wave + NW * q) * 1024), 16, 0, 0);
+        for (int q = 0; q < 2; ++q) dma16(wb + b_off[q], dst + (wave + NW * q) * 1024);
     };
     // prologue of a tile: A0 B0 B1 (0), A1 (0), A0 B0 B1 (1)
     auto prologue = [&]() {
@@ -187,7 +169,7 @@ __global__ __launch_bounds__(512) void gemm4_kernel(const GemmDesc d) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                af[i][ks] = *reinterpret_cast<const bf16v8*>(base + i * 16 * 128 + ((4 * ks + g) ^ (fr & 7)) * 16);
+                af[i][ks] = *reinterpret_cast<const bf16v8*>(base + i * 16 * 128 + swz_slot(ks, g, fr));
     };
     auto readB = [&](int buf, int nh, bf16v8 (&bf)[2][2]) {
         const char* base = smem + (buf * 4 + 2 + nh) * G4_SLOT + (wc * 32 + fr) * 128;
@@ -195,7 +177,7 @@ __global__ __launch_bounds__(512) void gemm4_kernel(const GemmDesc d) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
-                bf[j][ks] = *reinterpret_cast<const bf16v8*>(base + j * 16 * 128 + ((4 * ks + g) ^ (fr & 7)) * 16);
+                bf[j][ks] = *reinterpret_cast<const bf16v8*>(base + j * 16 * 128 + swz_slot(ks, g, fr));
     };
 
     f32x4_t acc[TM][TN];
@@ -241,8 +223,8 @@ __global__ __launch_bounds__(512) void gemm4_kernel(const GemmDesc d) {
             const int buf = t & 1;
             const bool has1 = t + 1 < nk, has2 = t + 2 < nk;
             // phase A: after A0B0B1(t): A1(t) [2] + A0B0B1(t+1) [6]
-            if (has1) vm_wait<8>();
-            else vm_wait<2>();
+            if (has1) wait_vm<8>();
+            else wait_vm<2>();
             phase_barrier();
             if (t < 2 || t == nk - 1) mark();
             if (has1) issueA(t + 1, 1);
@@ -254,8 +236,8 @@ __global__ __launch_bounds__(512) void gemm4_kernel(const GemmDesc d) {
             quad(0, 1, af, bf1);
             G4_PRIO(0);
             // phase B: after A1(t): A0B0B1(t+1) [6] + A1(t+1) [2]
-            if (has1) vm_wait<8>();
-            else vm_wait<0>();
+            if (has1) wait_vm<8>();
+            else wait_vm<0>();
             phase_barrier();
             if (has2) {
                 issueA(t + 2, 0);
@@ -292,7 +274,7 @@ __global__ __launch_bounds__(512) void gemm4_kernel(const GemmDesc d) {
         if (!PERSIST || next >= ntiles) break;
         tile = next;
         // the epilogue's stores sit behind the staged K-tiles on the VM counter: drain all, then the next tile's bias
-        vm_wait<0>();
+        wait_vm<0>();
         load_bias4<TN>(d, n0, wn0, lane, bias4);
     }
 #ifdef ATHD_G4_STAMP
@@ -321,22 +303,10 @@ static void launch4f(const GemmDesc& d, hipStream_t s) {
     const int64_t tiles = ((M + 255) / 256) * ((d.N + 255) / 256);
     int64_t grid = tiles;
     if constexpr ((F & (F_RES | F_STATS)) == 0) {   // persistent: the resident blocks (one per CU), a multiple of 8
-        static int resident = 0;
-        if (resident == 0) {
-            int per_cu = 0, cus = 0, dev = 0;
-            (void)hipGetDevice(&dev);
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm4_kernel<F>, 512, 0);
-            resident = per_cu > 0 && cus > 0 ? per_cu * cus / 8 * 8 : -1;
-        }
+        const int64_t resident = resident_blocks<gemm4_kernel<F>>(512) / 8 * 8;
         if (resident >= 8 && resident < tiles) grid = resident;
     }
-    KScope ks(s);
-    if (ks.on()) {
-        double fl, by;
-        gemm_work(d, 1, fl, by);
-        ks.begin(klabel("gemm4_kernel<%u>", F), fl, by);
-    }
+    GemmScope ks(s, d, 1, "gemm4_kernel<%u>", F);
     hipLaunchKernelGGL((gemm4_kernel<F>), dim3((unsigned)grid), dim3(512), 0, s, with_fastdiv(d));
 }
 
@@ -347,13 +317,7 @@ extern "C" int athd_g4_stamp_set(uint64_t* p) {
 #endif
 
 int gemm4_launch(const GemmDesc& d, hipStream_t s) {
-    switch (epi_flags(d)) {
-#define ATHD_CASE(FL) \
-    case (FL): launch4f<(FL)>(d, s); break;
-        ATHD_EPI_LIST(ATHD_CASE)
-#undef ATHD_CASE
-        default: launch4f<F_ALL>(d, s); break;
-    }
+    dispatch_epi(epi_flags(d), [&](auto f) { launch4f<decltype(f)::value>(d, s); });
     return (int)hipGetLastError();
 }
 

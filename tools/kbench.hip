@@ -1,18 +1,13 @@
 // Kernel micro-benchmark entry points (test tooling, not part of libathd.so): plain-C launchers for the GEMM and
 // attention kernels on caller-provided device buffers, used by tools/kbench.py to time variants against
 // torch/hipBLASLt on identical shapes in one process.
-#include "../audio-to-sheet-music_amd/csrc/gemm.h"
+#include "../audio-to-sheet-music_amd/csrc/gemm_launch.h"
 #include "../audio-to-sheet-music_amd/csrc/attn.h"
 #include <hip/hip_runtime.h>
 
 using namespace athd;
 namespace athd {
 extern int g_attn_variant;
-int gemm2_launch(const GemmDesc& d, hipStream_t s);
-int gemm3_launch(const GemmDesc& d, hipStream_t s, int variant);
-int gemm4_launch(const GemmDesc& d, hipStream_t s);
-int gemm5_launch(const GemmDesc& d, hipStream_t s);
-int gemm5_probe_launch(const GemmDesc& d, hipStream_t s, int probe);
 }
 
 extern "C" {
@@ -30,7 +25,7 @@ int kb_gemm(int variant, const void* A, int a_bf16, const void* W, const float* 
     if (variant == 41) { d.store = 0; return gemm4_launch(d, (hipStream_t)stream); }   // timing probe: no C stores
     if (variant == 42) { d.bias = nullptr; return gemm4_launch(d, (hipStream_t)stream); }   // timing probe: no bias
     if (variant == 2) return gemm2_launch(d, (hipStream_t)stream);
-    if (variant >= 30) return gemm3_launch(d, (hipStream_t)stream, variant - 30);
+    if (variant >= 30) return gemm3_variant_launch(d, (hipStream_t)stream, variant - 30);
     return gemm_launch(d, 1, (hipStream_t)stream);
 }
 // residual-stream GEMM as the transformer's out_proj / linear2 run it: C (f32, in place) = C + scale * (A @ W^T + bias),
@@ -42,7 +37,7 @@ int kb_gemm_res(int variant, const void* A, const void* W, const float* bias, fl
     d.Wp = W; d.N = N; d.K = K; d.Kp = Kp; d.bias = bias; d.C = C; d.c_bf16 = 0; d.H_out_total = M; d.ldo = N;
     d.res = C; d.res_scale = scale; d.stats = stats;
     if (variant == 50) return N % 256 == 0 ? gemm5_launch(d, (hipStream_t)stream) : -1;
-    if (variant >= 30) return gemm3_launch(d, (hipStream_t)stream, variant - 30);
+    if (variant >= 30) return gemm3_variant_launch(d, (hipStream_t)stream, variant - 30);
     return gemm_launch(d, 1, (hipStream_t)stream);
 }
 // ConvT residue-pair GEMM as the decoder runs it (kept mode, pair 0): A (nb, H, W, Cin) bf16, 2 taps (rows u-1, u),
@@ -57,7 +52,7 @@ int kb_convt(int variant, const void* A, const void* W, const float* bias, void*
     d.C = C; d.c_bf16 = 1; d.ldo = Cout; d.stats = stats; d.col_split = Cout;
     d.H_out_total = 2 * H; d.o_stride = 2; d.o_off = 0; d.hi_row_off = 0; d.store_mask = 2;
     if (variant == 2) return gemm2_launch(d, (hipStream_t)stream);
-    if (variant >= 30) return gemm3_launch(d, (hipStream_t)stream, variant - 30);
+    if (variant >= 30) return gemm3_variant_launch(d, (hipStream_t)stream, variant - 30);
     return gemm_launch(d, 1, (hipStream_t)stream);
 }
 // four-residue ConvT GEMM as the decoder runs it for level 2 (kept mode): K = rows u-1 | u | u+1, N = 4*Cout split
@@ -73,7 +68,7 @@ int kb_convt_quad(int variant, int kskip, const void* A, const void* W, const fl
     if (kskip) d.k_blk = Cin;
     if (kskip == 2) d.store_mask = 0;       // probe: no stores
     if (kskip == 3) d.stats = nullptr;      // probe: no statistics
-    return gemm3_launch(d, (hipStream_t)stream, variant);
+    return gemm3_variant_launch(d, (hipStream_t)stream, variant);
 }
 // variant: 0 = attn32<2>, 1 = attn_bf16 (16x16x32), 2 = attn32<3>; prescaled = Q already x ATTN_Q_PRESCALE
 int kb_attn(int variant, int prescaled, const void* qkv, int nb, int N, void* out, void* stream) {
