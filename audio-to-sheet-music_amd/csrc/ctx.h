@@ -105,6 +105,41 @@ inline int dconv_rewrite_perm(int k) {
     const int ks = k / 32, g = (k % 32) / 8, i = k % 8;
     return 32 * ks + (i < 4 ? 4 * g + i : 16 + 4 * g + (i - 4));
 }
+// The last decoder level folded with its 1x1 output projection (dec_last.hip's header), in double.  w: ConvT weight
+// [48][4][8], b: its bias [4], P: freq_out / time_out weight [2][4], pb: its bias [2]; br 0 = freq, 1 = time.
+//   freq: [Am | A0 | Ap] (3 x [2][48]: P W7 / 2, P (W3 + W4) / 2, P W0 / 2), P b + pb (2), 0.1 P (8)
+//   time: Q_k = P W_k (8 x [2][48]), P b (2), pb (2), 0.1 P (8)
+inline std::vector<float> dec_last_fold(const std::vector<float>& w, const std::vector<float>& b,
+                                        const std::vector<float>& P, const std::vector<float>& pb, int br) {
+    const int cin = 48, co = 4;
+    auto pw = [&](int j, int ci, int k) {     // (P W_k)[j][ci]
+        double a = 0.0;
+        for (int cc = 0; cc < co; ++cc) a += (double)P[j * co + cc] * w[((size_t)ci * co + cc) * 8 + k];
+        return a;
+    };
+    double pbias[2];
+    for (int j = 0; j < 2; ++j) {
+        pbias[j] = 0.0;
+        for (int cc = 0; cc < co; ++cc) pbias[j] += (double)P[j * co + cc] * b[cc];
+    }
+    std::vector<float> f;
+    if (br == 0) {
+        for (int m = 0; m < 3; ++m)
+            for (int j = 0; j < 2; ++j)
+                for (int ci = 0; ci < cin; ++ci)
+                    f.push_back((float)(0.5 * (m == 0 ? pw(j, ci, 7) : m == 1 ? pw(j, ci, 3) + pw(j, ci, 4) : pw(j, ci, 0))));
+        for (int j = 0; j < 2; ++j) f.push_back((float)(pbias[j] + pb[j]));
+    } else {
+        for (int k = 0; k < 8; ++k)
+            for (int j = 0; j < 2; ++j)
+                for (int ci = 0; ci < cin; ++ci) f.push_back((float)pw(j, ci, k));
+        for (int j = 0; j < 2; ++j) f.push_back((float)pbias[j]);
+        for (int j = 0; j < 2; ++j) f.push_back(pb[j]);
+    }
+    for (int j = 0; j < 2; ++j)
+        for (int cc = 0; cc < co; ++cc) f.push_back((float)(0.1 * P[j * co + cc]));
+    return f;
+}
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t rup(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 constexpr int ENC_CH[4] = {48, 96, 192, 384};

@@ -682,6 +682,9 @@ __global__ __launch_bounds__(TL_NT) void tdec_tail_kernel(const DecLastDesc d) {
     o[1] = o1;
 }
 
+// which: 0 FL_DC, 1 FT_DC, 2 TL_IN, 3 TT_ROWS (test entries: ktest.cpp)
+int dec_last_const(int which) { return which == 0 ? FL_DC : which == 1 ? FT_DC : which == 2 ? TL_IN : TT_ROWS; }
+
 int fdec_tail_launch(const DecLastDesc& d, hipStream_t s) {
     if (d.g_bf16 != d.skip2_bf16 || d.g_bf16 != d.skip_bf16 || d.g_bf16 != d.fast_gelu ||d.P < 1 || d.NI % d.P != 0 || d.H < 1 || d.W < 1 || d.C_skip < 4 || d.H_skip < 1 || !d.g || !d.stats ||
         d.C_skip2 < DL_C || d.C_skip2 % 8 != 0 || d.H_skip2 < 1)

@@ -443,6 +443,9 @@ static int g_blocks() {
     return cus / G_NG * G_NG;
 }
 
+int fdec1_gram_wb() { return G_WB; }          // (test entries: ktest.cpp)
+int fdec1_gram_blocks() { return g_blocks(); }
+
 // partial slots per workgroup: the most items one tile range can meet
 static int g_kmax(int64_t NI, int W) {
     const int64_t NWB = (W + G_WB - 1) / G_WB, T = NI * NWB, Qg = g_blocks() / G_NG;

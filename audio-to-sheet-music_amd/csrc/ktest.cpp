@@ -13,6 +13,12 @@
 namespace athd {   // dconv.hip: the launchers' own shape predicates (no header declares them)
 bool dconv_conv3_supported(int C, int H, int kp, int64_t L);
 bool dconv_apply_supported(int C, int H, int kp, int64_t M);
+// norm.hip, dec_last.hip, fdec1f.hip: the tuning constants next to their launchers
+int dec_merge_run();
+int dec_merge_maxp();
+int dec_last_const(int which);
+int fdec1_gram_wb();
+int fdec1_gram_blocks();
 }  // namespace athd
 
 using namespace athd;
@@ -238,6 +244,90 @@ void kt_conv1x1_moments(const float* w, const float* b, int64_t N, int64_t H, in
     const std::vector<float> g = conv1x1_moments(std::vector<float>(w, w + N * H), std::vector<float>(b, b + N),
                                                  (int)N, (int)H, round_bf16 != 0);
     memcpy(out, g.data(), g.size() * sizeof(float));
+}
+
+// ---- the decoder kernels and the folded last level ----
+struct KtMerge {
+    void* src; int64_t src_bf16, H_src, kept, C; void* stats; int64_t gn_count; void* gn_w; void* gn_b;
+    void* skip; int64_t skip_bf16, H_skip, C_skip, P; void* out; int64_t out_bf16, H_out, W, NI;
+    void* proj_w; void* proj_b; int64_t fast_gelu;
+};
+struct KtLowRank {
+    void* steps; void* Z; void* Zs; int64_t z_bf16, z_taps, Hs, Hk, Hd, W, Co, P, NI; void* bias; void* stats;
+    void* gn_w; void* gn_b; int64_t fast_gelu; void* skip; int64_t skip_bf16, H_skip, C_skip; void* out; int64_t out_bf16;
+    void* S; void* Wt; int64_t w_ld, Ci; void* z4; void* gram; void* gq;
+};
+struct KtDecLast {
+    void* in; int64_t in_bf16, NI, P, H, W, T; void* fold; void* skip; int64_t skip_bf16, H_skip, C_skip; void* out;
+    void* g; int64_t g_bf16, Hg; void* stats; int64_t gn_count; void* gn_w; void* gn_b; int64_t fast_gelu;
+    void* skip2; int64_t skip2_bf16, H_skip2, C_skip2;
+};
+int64_t kt_sizeof_merge() { return (int64_t)sizeof(KtMerge); }
+int64_t kt_sizeof_lowrank() { return (int64_t)sizeof(KtLowRank); }
+int64_t kt_sizeof_declast() { return (int64_t)sizeof(KtDecLast); }
+int64_t kt_sizeof_lrstep() { return (int64_t)sizeof(LrStep); }
+
+int kt_dec_merge(const KtMerge* k, void* stream) {
+    MergeDesc d;
+    d.src = k->src; d.src_bf16 = (int)k->src_bf16; d.H_src = (int)k->H_src; d.kept = (int)k->kept; d.C = (int)k->C;
+    d.stats = (const double*)k->stats; d.gn_count = k->gn_count; d.gn_w = (const float*)k->gn_w;
+    d.gn_b = (const float*)k->gn_b; d.skip = k->skip; d.skip_bf16 = (int)k->skip_bf16; d.H_skip = (int)k->H_skip;
+    d.C_skip = (int)k->C_skip; d.P = (int)k->P; d.out = k->out; d.out_bf16 = (int)k->out_bf16; d.H_out = (int)k->H_out;
+    d.W = (int)k->W; d.NI = (int)k->NI; d.proj_w = (const float*)k->proj_w; d.proj_b = (const float*)k->proj_b;
+    d.fast_gelu = (int)k->fast_gelu;
+    return dec_merge_launch(d, (hipStream_t)stream);
+}
+static LowRankDesc to_lr(const KtLowRank* k) {
+    LowRankDesc d;
+    d.steps = (const LrStep*)k->steps; d.Z = k->Z; d.Zs = k->Zs; d.z_bf16 = (int)k->z_bf16; d.z_taps = (int)k->z_taps;
+    d.Hs = (int)k->Hs; d.Hk = (int)k->Hk; d.Hd = (int)k->Hd; d.W = (int)k->W; d.Co = (int)k->Co; d.P = (int)k->P;
+    d.NI = (int)k->NI; d.bias = (const float*)k->bias; d.stats = (double*)k->stats; d.gn_w = (const float*)k->gn_w;
+    d.gn_b = (const float*)k->gn_b; d.fast_gelu = (int)k->fast_gelu; d.skip = k->skip; d.skip_bf16 = (int)k->skip_bf16;
+    d.H_skip = (int)k->H_skip; d.C_skip = (int)k->C_skip; d.out = k->out; d.out_bf16 = (int)k->out_bf16;
+    d.S = k->S; d.Wt = k->Wt; d.w_ld = (int)k->w_ld; d.Ci = (int)k->Ci; d.z4 = k->z4;
+    return d;
+}
+int kt_fdec_lr_stats(const KtLowRank* k, void* stream) { return fdec_lr_stats_launch(to_lr(k), (hipStream_t)stream); }
+int kt_fdec_lr_merge(const KtLowRank* k, void* stream) { return fdec_lr_merge_launch(to_lr(k), (hipStream_t)stream); }
+int kt_fdec1_gram(const KtLowRank* k, void* stream) {
+    return fdec1_gram_launch(to_lr(k), (float*)k->gram, (double*)k->gq, (hipStream_t)stream);
+}
+int kt_fdec1_gram_supported(const KtLowRank* k) { return fdec1_gram_supported(to_lr(k)); }
+int kt_fdec_lr_steps(void* steps, int64_t Hd, int64_t Hs, int64_t Hk, int64_t H_skip, void* stream) {
+    return fdec_lr_steps_launch((LrStep*)steps, (int)Hd, (int)Hs, (int)Hk, (int)H_skip, (hipStream_t)stream);
+}
+int64_t kt_fdec1_gram_floats(int64_t NI, int64_t W) { return fdec1_gram_floats(NI, (int)W); }
+int64_t kt_fdec1_gram_q_doubles() { return fdec1_gram_q_doubles(); }
+static DecLastDesc to_dl(const KtDecLast* k) {
+    DecLastDesc d;
+    d.in = k->in; d.in_bf16 = (int)k->in_bf16; d.NI = (int)k->NI; d.P = (int)k->P; d.H = (int)k->H; d.W = (int)k->W;
+    d.T = k->T; d.fold = (const float*)k->fold; d.skip = k->skip; d.skip_bf16 = (int)k->skip_bf16;
+    d.H_skip = (int)k->H_skip; d.C_skip = (int)k->C_skip; d.out = (float*)k->out; d.g = k->g; d.g_bf16 = (int)k->g_bf16;
+    d.Hg = (int)k->Hg; d.stats = (const double*)k->stats; d.gn_count = k->gn_count; d.gn_w = (const float*)k->gn_w;
+    d.gn_b = (const float*)k->gn_b; d.fast_gelu = (int)k->fast_gelu; d.skip2 = k->skip2; d.skip2_bf16 = (int)k->skip2_bf16;
+    d.H_skip2 = (int)k->H_skip2; d.C_skip2 = (int)k->C_skip2;
+    return d;
+}
+int kt_fdec_last(const KtDecLast* k, void* stream) { return fdec_last_launch(to_dl(k), (hipStream_t)stream); }
+int kt_tdec_last(const KtDecLast* k, void* stream) { return tdec_last_launch(to_dl(k), (hipStream_t)stream); }
+int kt_fdec_tail(const KtDecLast* k, void* stream) { return fdec_tail_launch(to_dl(k), (hipStream_t)stream); }
+int kt_tdec_tail(const KtDecLast* k, void* stream) { return tdec_tail_launch(to_dl(k), (hipStream_t)stream); }
+int kt_tdec_tail_supported(const KtDecLast* k) { return tdec_tail_supported(to_dl(k)); }
+// the constants the tests' shape lists depend on
+int64_t kt_fl_dc() { return dec_last_const(0); }
+int64_t kt_ft_dc() { return dec_last_const(1); }
+int64_t kt_tl_in() { return dec_last_const(2); }
+int64_t kt_tt_rows() { return dec_last_const(3); }
+int64_t kt_dm_run() { return dec_merge_run(); }
+int64_t kt_merge_maxp() { return dec_merge_maxp(); }
+int64_t kt_g_wb() { return fdec1_gram_wb(); }
+int64_t kt_fdec1_gram_blocks() { return fdec1_gram_blocks(); }      // (queries the current device's CU count)
+// ctx.h dec_last_fold (host): w [48][4][8], b [4], P [2][4], pb [2] -> out (br 0: 298 floats, br 1: 780)
+int64_t kt_dec_last_fold(const float* w, const float* b, const float* P, const float* pb, int64_t br, float* out) {
+    const std::vector<float> f = dec_last_fold(std::vector<float>(w, w + 48 * 4 * 8), std::vector<float>(b, b + 4),
+                                               std::vector<float>(P, P + 8), std::vector<float>(pb, pb + 2), (int)br);
+    if (out) memcpy(out, f.data(), f.size() * sizeof(float));
+    return (int64_t)f.size();
 }
 
 int kt_gn_apply(float* x, int64_t nb, int64_t N, int64_t C, const double* stats, const float* w, const float* b,

@@ -955,6 +955,8 @@ __global__ __launch_bounds__(256) void dec_merge_proj_kernel(const MergeDesc d) 
     }
 }
 
+int dec_merge_run() { return DM_RUN; }        // (test entries: ktest.cpp)
+int dec_merge_maxp() { return MERGE_MAXP; }
 int dec_merge_launch(const MergeDesc& d, hipStream_t s) {
     if (d.P < 1 || d.P > MERGE_MAXP || d.NI % d.P != 0) return -1;
     const int V = (d.C % 8 == 0) ? 8 : 4;    // C is 192/96/48 (8) or 4

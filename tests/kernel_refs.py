@@ -1,5 +1,5 @@
 """float64 references and derived tolerances for the kernel-level parity tests (tests/test_gpu_kernels.py,
-tests/test_gpu_dconv.py).
+tests/test_gpu_dconv.py, tests/test_gpu_dec.py).
 
 Every reference is written from the operation's formula (csrc/gemm.h's header comment, csrc/attn.h, csrc/kernels.h),
 not from a kernel.  Beside every result R it returns tol, an error bound derived from the number formats:
@@ -77,6 +77,33 @@ SURVEY.md Appendix A: conv3 -> GroupNorm(1) -> GELU -> 1x1 -> GroupNorm(1) -> GL
   shows finite values of the right order.  tests/test_dconv_refs.py holds the measured figures and asserts them.
 * Short GroupNorm rows (L = 1, 2 in dconv_small) have a tiny variance, so rstd is large (up to 316) and every bound
   above that carries r grows with it.  That is the arithmetic's own conditioning, not slack.
+
+The decoder kernels (tests/test_gpu_dec.py; formulas: csrc/kernels.h, the header comments of csrc/fdec_lr.hip and
+csrc/dec_last.hip, ATHTDemucs_v2.py:76-139 as cited there) add:
+
+* The resize index rule (common.h lin_index) is evaluated in float32 exactly as the device does, the multiply-add of
+  the source index fused (lin_index_ref), so the references use the kernels' own lerp weights bit for bit and no bound
+  carries a weight error.  A lerp l0 a + l1 b adds 3e (l0 |a| + l1 |b|) (two products, one sum) to the resized input
+  bounds (resize_h_ref); an identity resize adds nothing.
+* The decoder merge (dec_merge_ref): GroupNorm from the exact fp64 {sum, sumsq} the kernel reads (dm = drr = 0; the
+  float32 roundings of mean and rstd are part of the 4e terms), gelu_step or gelu_tanh_step, the resize, the skip
+  0.1 resize(skip) (2e for the float32 0.1 and the product), 2e for the sum; the 1x1 projection: |P| tol + (C + 4) e
+  |P| |v|; hulp16 at |R| + tol for a bf16 store.  Where a kernel folds the affine into x (r w) + (b - m r w) (the bf16
+  forms of dec_merge_w1, fdec_tail, tdec_tail, fdec_lr_merge3), x and m no longer cancel before the roundings:
+  + 6e (|x| + |m|) r |w| + 4e |b|.  Two GELUs sharing one reciprocal (gelu_fast_wsum_pk): + 8e of each weighted term.
+  tdec_tail keeps the activated rows as bf16 in LDS: the reference rounds them too and bf16_round_amb gives the bound
+  (the rounded value feeds the resize and the folded projection).
+* The folded last level (dec_last_ref) is computed from the unfolded weights; the kernels get the product's fold.
+  tol = (K + 32) e A, A the same chain on absolute values, K = 3 x 48 (freq) or 4 x 48 (time) accumulated products;
+  the 32 covers the fold's own float32 rounding (e |P| |W|), the skip products and the last sums.  A bound on the
+  input (the fused level-2 merge) goes through |W|, the resize and |P|.
+* The low-rank level 1 (fdec_lr_ref) is staged: Z, Zs are the stored roundings of float64 products and stand for S and
+  skip3 (resize and ConvTranspose commute with the per-tap 1x1); D0 is materialised and the plain ConvTranspose scatter
+  runs on it, the re-association does not appear.  Per D0 value: the two resize bounds + 2e; per ConvT row: the sum of
+  its D0 bounds + 3e (|terms| + |bias|).  The v3 passes update the lerp base incrementally (base += dr at every row
+  change): one float32 rounding of the base per change, e (|Z[i0]| + 0.1 |Zs[k0]| + |bias|), accumulated over the
+  changes counted from the step table up to the row's step.  {sum, sumsq}: the statistics rule with n_part = 68 (16
+  steps x 4 rows per float32 partial sum) and the fp64 additions above it.
 """
 import math
 from types import SimpleNamespace
@@ -795,3 +822,314 @@ def fenc_row_ref(level, p, xin, a_norm, f, Fin, row_add=None, mut=None):
     elif level == 0:
         ra = np.zeros(C)
     return dconv_rewrite_ref(x, d, p["wr"], p["br"], row_add=ra)
+
+
+# ------------------------------------------------------------------------------------------------ decoder
+SKIP_GAIN = 0.1               # ATHTDemucs_v2.py:102 / :137: x + 0.1 * resize(skip)
+
+
+def lin_index_ref(in_size, out_size, fma=True):
+    """common.h lin_index for dst = 0 .. out_size - 1 in float32 -> (i0, i1, l0, l1) (int64, int64, float32, float32).
+    fma: src = scale (dst + 0.5) - 0.5 rounded once (the device compiler contracts the multiply-add; the product of two
+    float32 and the - 0.5 are exact in float64 for sizes below 2^24, so one rounding of the float64 value is the fused
+    result); False: the product rounded first (a host build without fused multiply-add)."""
+    f = np.float32
+    d = np.arange(out_size)
+    if in_size == out_size:
+        return d.copy(), d.copy(), np.ones(out_size, dtype=f), np.zeros(out_size, dtype=f)
+    scale = f(in_size) / f(out_size)
+    t = d.astype(f) + f(0.5)
+    if fma:
+        src = (t.astype(np.float64) * np.float64(scale) - 0.5).astype(f)
+    else:
+        src = (t * scale).astype(f) - f(0.5)
+    src = np.maximum(src, f(0))
+    i0 = np.minimum(np.floor(src).astype(np.int64), in_size - 1)
+    lam = np.clip(src - i0.astype(f), f(0), f(1)).astype(f)
+    i1 = i0 + (i0 < in_size - 1)
+    return i0, i1, (f(1) - lam).astype(f), lam
+
+
+def lin_slack(in_size, out_size):
+    """bound on the change of a lerp weight when scale (dst + 0.5) is rounded before the - 0.5 (lin_index_ref's two
+    forms): one rounding of a product below in_size.  Not part of any kernel bound: the device evaluates the fused form
+    bit for bit (tests/test_gpu_dec.py test_fdec_lr_steps), so the references use the kernels' own weights."""
+    return 0.0 if in_size == out_size else E32 * in_size
+
+
+def resize_h_ref(x, H_out, axis=1, tol=None, mut=None):
+    """linear resize of x along `axis` by lin_index_ref (float64 values, float32 weights) -> (R, T): T = the resized
+    input bound `tol` + 3e (l0 |a| + l1 |b|) (two products, one sum).  Equal sizes: the identity, (x, tol).
+    mut 'i1_as_i0': row i1 taken as i0."""
+    x = np.asarray(x, dtype=np.float64)
+    t = np.zeros_like(x) if tol is None else np.broadcast_to(np.asarray(tol, dtype=np.float64), x.shape)
+    H_in = x.shape[axis]
+    if H_in == H_out:
+        return x.copy(), t.copy()
+    i0, i1, l0, l1 = lin_index_ref(H_in, H_out)
+    if mut == "i1_as_i0":
+        i1 = i0
+    sh = [1] * x.ndim
+    sh[axis] = H_out
+    l0, l1 = l0.astype(np.float64).reshape(sh), l1.astype(np.float64).reshape(sh)
+    a, b = np.take(x, i0, axis=axis), np.take(x, i1, axis=axis)
+    T = l0 * np.take(t, i0, axis=axis) + l1 * np.take(t, i1, axis=axis)
+    T = T + 3 * E32 * (l0 * np.abs(a) + l1 * np.abs(b))
+    return l0 * a + l1 * b, T
+
+
+def dec_merge_ref(src, skip, H_out, P, stats=None, gn_count=0, gn_w=None, gn_b=None, fast=False, folded=False,
+                  kept=False, proj_w=None, proj_b=None, out_bf16=False, act_bf16=False, wsum=False, d_src=None,
+                  mut=None):
+    """kernels.h MergeDesc: out[item][ho][w][c] = resize_H(act(GN(src)))[ho][w][c] + 0.1 resize_H(skip[item / P])[..][c]
+    (ATHTDemucs_v2.py:88-103 / :126-138).  src [NI][H_src][W][C] logical ConvT rows (float64 values as stored), skip
+    [NI / P][H_skip][W][C_skip >= C]; stats: the fp64 {sum, sumsq} per item the kernel reads (exact inputs, dm = drr =
+    0; None: no GroupNorm and no activation); fast: the tanh GELU (gelu_tanh_step), else erf (gelu_step); folded: the
+    affine evaluated as x (r w) + (b - m r w) (adds 6e (|x| + |m|) r |w| + 4e |b|: x and m no longer cancel before the
+    roundings); act_bf16: the activated rows are rounded to bf16 before the resize (tdec_tail's LDS tile); wsum: the
+    two GELUs of a resize share one reciprocal (common.h gelu_fast_wsum_pk: + 8e of each weighted term); d_src: bound
+    on src itself.  kept: only rows 4d + 1, 4d + 2 of src exist (the others are NaN here: they must not be read).
+    proj_w [2][C], proj_b [2]: the 1x1 projection, out [NI][W][H_out][2].  Returns (R, tol).
+    mut: 'i1_as_i0', 'skip_next_seg', 'skip_prompt' (the skip rows of the segment of item + 1), 'no_gain' (the 0.1
+    dropped), 'gn_next_item' (GroupNorm statistics of item n + 1)."""
+    src = np.asarray(src, dtype=np.float64)
+    skip = np.asarray(skip, dtype=np.float64)
+    NI, H_src, W, C = src.shape
+    nseg = NI // P
+    a = src.copy()
+    ta = np.zeros_like(a) if d_src is None else np.array(d_src, dtype=np.float64)
+    if kept:
+        dead = np.ones(H_src, dtype=bool)
+        dead[1::4] = dead[2::4] = False
+        a[:, dead] = np.nan
+    if stats is not None:
+        st = np.asarray(stats, dtype=np.float64).reshape(NI, 2)
+        if mut == "gn_next_item":
+            st = np.roll(st, -1, axis=0)
+        m, r = gn_params(st, gn_count)
+        m, r = m[:, None, None, None], r[:, None, None, None]
+        w, b = np.asarray(gn_w, dtype=np.float64), np.asarray(gn_b, dtype=np.float64)
+        c = (a - m) * r * w
+        tz = np.abs(w) * r * ta + 4 * E32 * (np.abs(c) + np.abs(b) + np.abs(m) * r * np.abs(w))
+        if folded:
+            tz = tz + 6 * E32 * (np.abs(a) + np.abs(m)) * r * np.abs(w) + 4 * E32 * np.abs(b)
+        z = c + b
+        if fast:
+            a, ta = gelu_tanh_step(z, tz)
+        else:
+            a, ta = gelu_step(z, tz, False)
+        if act_bf16:
+            a, amb = bf16_round_amb(a, ta)
+            ta = amb              # (the rounding itself is exact in the reference; amb: the kernel's other neighbour)
+    with np.errstate(invalid="ignore"):
+        mres, tm = resize_h_ref(a, H_out, axis=1, tol=ta, mut=mut)
+    if wsum and H_src != H_out:
+        i0, i1, l0, l1 = lin_index_ref(H_src, H_out)
+        sh = (1, H_out, 1, 1)
+        tm = tm + 8 * E32 * (l0.reshape(sh) * np.abs(np.take(a, i0, axis=1)) + l1.reshape(sh) * np.abs(np.take(a, i1, axis=1)))
+    sk, tsk = resize_h_ref(skip[..., :C], H_out, axis=1)
+    g = 1.0 if mut == "no_gain" else SKIP_GAIN
+    sk, tsk = g * sk, g * tsk + 2 * E32 * g * np.abs(sk)         # (the float32 0.1 and the product)
+    seg = np.arange(NI) // P
+    if mut == "skip_next_seg":
+        seg = (seg + 1) % nseg
+    elif mut == "skip_prompt":
+        seg = ((np.arange(NI) + 1) // P) % nseg
+    v = mres + sk[seg]
+    tv = tm + tsk[seg] + 2 * E32 * (np.abs(mres) + np.abs(sk[seg]))
+    if proj_w is not None:
+        pw, pb = np.asarray(proj_w, dtype=np.float64), np.asarray(proj_b, dtype=np.float64)
+        o = v @ pw.T + pb
+        to = tv @ np.abs(pw).T + (C + 4) * E32 * (np.abs(v) @ np.abs(pw).T + np.abs(pb))
+        return np.transpose(o, (0, 2, 1, 3)).copy(), np.transpose(to, (0, 2, 1, 3)).copy()
+    if out_bf16:
+        tv = tv + hulp16(np.abs(v) + tv)
+    return v, tv
+
+
+def dec_last_fold_ref(w, b, P, pb, br):
+    """the fold of dec_last.hip's header in float64 (not rounded): freq [Am | A0 | Ap] (3 x [2][48]), P b + pb (2),
+    0.1 P (8); time Q_k (8 x [2][48]), P b (2), pb (2), 0.1 P (8)"""
+    w, b, P, pb = (np.asarray(v, dtype=np.float64) for v in (w, b, P, pb))
+    Q = np.einsum("jc,ick->kji", P, w)                 # Q[k][j][ci] = sum_c P[j][c] w[ci][c][k]
+    if br == 0:
+        return np.concatenate([(0.5 * Q[7]).ravel(), (0.5 * (Q[3] + Q[4])).ravel(), (0.5 * Q[0]).ravel(), P @ b + pb,
+                               (0.1 * P).ravel()])
+    return np.concatenate([Q.ravel(), P @ b, pb, (0.1 * P).ravel()])
+
+
+def dec_last_ref(br, x, w, b, Pm, pb, skip, P, T=None, d_in=None, mut=None):
+    """The last decoder level from the unfolded weights (dec_last.hip's header; ATHTDemucs_v2.py:76-104 / :125-139 with
+    i = 3, then freq_out / time_out): ConvTranspose (k8 s4 p2) 48 -> 4 over H, linear resize 4H -> H (freq) or T (time),
+    + 0.1 resize(skip[item / P][..., :4]), 1x1 projection Pm [2][4] + pb.
+    freq (br 0): x [NI][H][W][48], skip [NI / P][H_skip][W][C_skip] -> out [NI][W][H][2];
+    time (br 1): x [NI][H][48], skip [NI / P][H_skip][C_skip] -> out [NI][T][2].
+    tol = (K + 32) e A with A the same chain on absolute values and K = 3 x 48 (freq: three folded matrices) or 4 x 48
+    (time: two ConvT rows of two taps each); the + 32 covers the folded weights' own float32 rounding (e of |P| |W|),
+    the skip products and the final sums; + the resize bounds of resize_h_ref through |Pm|; d_in: bound on x, carried
+    through |w|, the resizes and |Pm|.
+    mut: 'taps34' (taps 3 and 4 swapped), 'am_ap' (taps 7 and 0: Am and Ap swapped), 'no_bias' (ConvT bias dropped),
+    'no_gain', 'skip_next_seg', 'skip_prompt', 'i1_as_i0' (of the skip resize)."""
+    x = np.asarray(x, dtype=np.float64)
+    skip = np.asarray(skip, dtype=np.float64)
+    w = np.array(w, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    Pm, pb = np.asarray(Pm, dtype=np.float64), np.asarray(pb, dtype=np.float64)
+    if br == 1:
+        x, skip = x[:, :, None, :], skip[:, :, None, :]
+        if d_in is not None:
+            d_in = np.asarray(d_in)[:, :, None, :]
+    NI, H = x.shape[0], x.shape[1]
+    Ho = H if br == 0 else int(T)
+    if mut == "taps34":
+        w[:, :, [3, 4]] = w[:, :, [4, 3]]
+    elif mut == "am_ap":
+        w[:, :, [0, 7]] = w[:, :, [7, 0]]
+    bb = np.zeros_like(b) if mut == "no_bias" else b
+    y, S = convt_ref_direct(x, w, bb)
+    ty = np.zeros_like(y) if d_in is None else convt_ref_direct(np.asarray(d_in, dtype=np.float64), np.abs(w), 0 * b)[0]
+    yr, tyr = resize_h_ref(y, Ho, axis=1, tol=ty)
+    Sr, _ = resize_h_ref(S, Ho, axis=1)
+    sk, tsk = resize_h_ref(skip[..., :4], Ho, axis=1, mut=mut if mut == "i1_as_i0" else None)
+    ska, _ = resize_h_ref(np.abs(skip[..., :4]), Ho, axis=1)
+    g = 1.0 if mut == "no_gain" else SKIP_GAIN
+    seg = np.arange(NI) // P
+    nseg = NI // P
+    if mut == "skip_next_seg":
+        seg = (seg + 1) % nseg
+    elif mut == "skip_prompt":
+        seg = ((np.arange(NI) + 1) // P) % nseg
+    v = yr + g * sk[seg]
+    A = (Sr + g * ska[seg]) @ np.abs(Pm).T + np.abs(pb)
+    K = 3 * 48 if br == 0 else 4 * 48
+    out = v @ Pm.T + pb
+    tol = (K + 32) * E32 * A + (tyr + g * tsk[seg]) @ np.abs(Pm).T
+    if br == 0:
+        return np.transpose(out, (0, 2, 1, 3)).copy(), np.transpose(tol, (0, 2, 1, 3)).copy()
+    return out[:, :, 0], tol[:, :, 0]
+
+
+def lr_steps_ref(Hd, Hs, Hk, H_skip):
+    """the step table of kernels.h LrStep, Hd + 1 entries, as a dict of arrays: step v < Hd holds the Z (Hs -> Hd) and
+    skip-projection (Hk -> Hd) lerps of row v; step v >= 1 the skip (H_skip -> Hd) lerp of row v - 1; flag bits 0 / 1 /
+    2: the z / k / j rows differ from the previous step's (set at their first step: v = 0, 0, 1; clear where the rows
+    are not defined).  Entries that are not defined hold -1 (masked to the field width by the packing)."""
+    z0, z1, _, lz = lin_index_ref(Hs, Hd)
+    k0, k1, _, lk = lin_index_ref(Hk, Hd)
+    j0, j1, _, lj = lin_index_ref(H_skip, Hd)
+    n = Hd + 1
+    out = {k_: np.full(n, -1, dtype=np.int64) for k_ in ("z0", "z1", "k0", "k1", "j0", "j1")}
+    out["z0"][:Hd], out["z1"][:Hd], out["k0"][:Hd], out["k1"][:Hd] = z0, z1, k0, k1
+    out["j0"][1:], out["j1"][1:] = j0, j1
+    out["lz"], out["lk"], out["lj"] = (np.zeros(n, dtype=np.float32) for _ in range(3))
+    out["lz"][:Hd], out["lk"][:Hd], out["lj"][1:] = lz, lk, lj
+    fl = np.zeros(n, dtype=np.int64)
+    for bit, (a, b_), lo, hi in ((1, ("z0", "z1"), 0, Hd), (2, ("k0", "k1"), 0, Hd), (4, ("j0", "j1"), 1, n)):
+        ch = np.ones(n, dtype=bool)
+        ch[1:] = (out[a][1:] != out[a][:-1]) | (out[b_][1:] != out[b_][:-1])
+        ch[:lo] = False
+        ch[hi:] = False
+        ch[lo] = True
+        fl |= np.where(ch, bit, 0)
+    out["flags"] = fl
+    return out
+
+
+def fdec_lr_ref(Z, Zs, bias, Hd, P, v3=False):
+    """FreqDecoder level 1 from the tap products (fdec_lr.hip's header; ATHTDemucs_v2.py:90-103): Z [NI][Hs][W][8][Co]
+    = W_k S[j] and Zs [NI / P][Hk][W][8][Co] = W_k skip3[m] as stored (the resize and the ConvTranspose commute with
+    the per-tap 1x1, so the stored products stand for S and skip3).  D0 = resize_H(Z, Hs -> Hd) + 0.1 resize_H(Zs, Hk ->
+    Hd) is materialised and the plain ConvTranspose (k8 s4 p2) scatter runs on it: Y[4u - 2 + k] += D0[u][k], + bias.
+    Returns (Y [NI][4 Hd][W][Co], tolY).  tolY: the resize bounds + 2e of the sum per D0 value, 3e (|terms| + |bias|)
+    per Y row; v3: the incremental base (base += dr at every row change) carries one float32 rounding of the base per
+    change: e (|Z[i0]| + 0.1 |Zs[k0]| + |bias|) accumulated over the changes of the step table up to the row's step."""
+    Z, Zs, bias = (np.asarray(v, dtype=np.float64) for v in (Z, Zs, bias))
+    NI, Hs, W, _, Co = Z.shape
+    Hk = Zs.shape[1]
+    seg = np.arange(NI) // P
+    a, ta = resize_h_ref(Z, Hd, axis=1)
+    s, ts = resize_h_ref(Zs, Hd, axis=1)
+    s, ts = SKIP_GAIN * s, SKIP_GAIN * ts + 2 * E32 * SKIP_GAIN * np.abs(s)
+    D0 = a + s[seg]
+    tD = ta + ts[seg] + 2 * E32 * (np.abs(a) + np.abs(s[seg]))
+    if v3:
+        st = lr_steps_ref(Hd, Hs, Hk, 1)
+        aZ, aS = np.abs(Z), SKIP_GAIN * np.abs(Zs)
+        drift = np.zeros_like(D0)
+        acc = np.zeros_like(D0[:, 0])
+        for u in range(Hd):
+            if u and st["flags"][u] & 1:
+                acc = acc + E32 * (aZ[:, st["z0"][u]] + aS[seg][:, st["k0"][u]] + np.abs(bias))
+            if u and st["flags"][u] & 2:
+                acc = acc + E32 * (aZ[:, st["z0"][u]] + aS[seg][:, st["k0"][u]] + np.abs(bias))
+            drift[:, u] = acc
+        tD = tD + drift
+    Y = np.zeros((NI, 4 * Hd, W, Co))
+    A = np.zeros_like(Y)
+    tY = np.zeros_like(Y)
+    for k in range(8):
+        o = 4 * np.arange(Hd) - 2 + k
+        ok = (o >= 0) & (o < 4 * Hd)
+        Y[:, o[ok]] += D0[:, :, :, k][:, ok]
+        A[:, o[ok]] += np.abs(D0[:, :, :, k][:, ok])
+        tY[:, o[ok]] += tD[:, :, :, k][:, ok]
+    return Y + bias, tY + 3 * E32 * (A + np.abs(bias))
+
+
+def fdec_lr_rows(Z, Zs, bias, Hd, P):
+    """the ConvT rows of fdec_lr_ref without their bounds (the same chain, values only)"""
+    Z, Zs, bias = (np.asarray(v, dtype=np.float64) for v in (Z, Zs, bias))
+    NI = Z.shape[0]
+
+    def lerp(x):
+        if x.shape[1] == Hd:
+            return x
+        i0, i1, l0, l1 = lin_index_ref(x.shape[1], Hd)
+        sh = (1, Hd, 1, 1, 1)
+        return l0.astype(np.float64).reshape(sh) * x[:, i0] + l1.astype(np.float64).reshape(sh) * x[:, i1]
+    D0 = lerp(Z) + (SKIP_GAIN * lerp(Zs))[np.arange(NI) // P]
+    Y = np.zeros((NI, 4 * Hd) + Z.shape[2:3] + Z.shape[4:])
+    for k in range(8):
+        o = 4 * np.arange(Hd) - 2 + k
+        ok = (o >= 0) & (o < 4 * Hd)
+        Y[:, o[ok]] += D0[:, :, :, k][:, ok]
+    return Y + bias
+
+
+def fdec_lr_stats_ref(Y, tY, Hd):
+    """{sum, sumsq} per item over all 4 Hd ConvT rows and their bound (the statistics rule): per thread at most 16 steps
+    x 4 rows are added in float32 (n_part = 68), then fp64 over Hd / 16 chunks, the wave, the block and the atomics"""
+    nblk = (Y.shape[2] * (Y.shape[3] // 2) + 255) // 256
+    return stats_of(Y, tY, n_part=68, n64=Hd // 16 + 16 + nblk)
+
+
+def gram_z_ref(S, Wt):
+    """Z = S W_k^T as the Gram pass holds it in LDS and stores it as z4 (fdec1f.hip's header): the bf16 rounding of a
+    float32 accumulation of exact bf16 products, K = Ci.  S [NI][Hs][W][Ci], Wt [8][Co][Ci] (bf16 values) -> (Zr, amb)
+    [NI][Hs][W][8][Co]: bf16_round_amb of the float64 product with the GEMM bound (K + 16) e |S| |W|."""
+    S, Wt = np.asarray(S, dtype=np.float64), np.asarray(Wt, dtype=np.float64)
+    sh = S.shape[:-1] + Wt.shape[:2]
+    W2 = Wt.reshape(-1, Wt.shape[-1])
+    Zx = (S.reshape(-1, S.shape[-1]) @ W2.T).reshape(sh)
+    Za = (np.abs(S).reshape(-1, S.shape[-1]) @ np.abs(W2).T).reshape(sh)
+    return bf16_round_amb(Zx, (S.shape[-1] + 16) * E32 * Za)
+
+
+def fdec1_gram_stats_ref(Zr, amb, Zs, bias, Hd, P):
+    """{sum, sumsq} per item over the 4 Hd ConvT rows of fdec_lr_ref on (Zr, Zs), and the bound of their evaluation as
+    quadratic forms of per-item Gram matrices (fdec1f.hip's header): the Gram entries and per-channel sums are float32
+    accumulations of exact bf16 products over the item's (w, c), 16 W per channel group, then the partial slots and the
+    6 groups: n = 16 W + 32 additions, each bounded by e times the form on absolute values (every lerp coefficient is
+    >= 0, so <Q, |x| |x|^T> is the sum of squares of the same chain on |Z|, |Zs|, |bias|: the cancellation between
+    sum b^2, 2 c1 . ub and <Q, G> at a large mean is inside it); the coefficients (double, from the float32 lambda) and
+    the final sums are fp64.  amb (gram_z_ref: Z elements the kernel may have rounded to the other neighbour) goes
+    through the same positive chain into the statistics rule."""
+    Y = fdec_lr_rows(Zr, Zs, bias, Hd, P)
+    tY = fdec_lr_rows(amb, 0.0 * np.asarray(Zs), 0.0 * np.asarray(bias), Hd, P)
+    Ya = fdec_lr_rows(np.abs(Zr), np.abs(Zs), np.abs(bias), Hd, P)
+    n = 16 * Zr.shape[2] + 32
+    ax = (1, 2, 3)
+    st = np.stack([Y.sum(axis=ax), (Y * Y).sum(axis=ax)], -1)
+    t1 = tY.sum(axis=ax) + n * E32 * Ya.sum(axis=ax)
+    t2 = (2 * np.abs(Y) * tY + tY * tY).sum(axis=ax) + n * E32 * (Ya * Ya).sum(axis=ax)
+    return st, np.stack([t1, t2], -1), Y

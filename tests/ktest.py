@@ -1,6 +1,7 @@
 """ctypes binding of libathd_ktest.so (csrc/ktest.cpp): the kernel launchers of libathd.so behind flat descriptors.
-A plain helper module of tests/test_gpu_kernels.py and tests/test_gpu_dconv.py; importing it needs the built libraries
-but no GPU (the host-side packers it exports are compared on the CPU, tests/test_dconv_refs.py)."""
+A plain helper module of tests/test_gpu_kernels.py, tests/test_gpu_dconv.py and tests/test_gpu_dec.py; importing it needs
+the built libraries but no GPU (the host-side packers, folds and shape predicates it exports are compared on the CPU,
+tests/test_dconv_refs.py, tests/test_dec_refs.py)."""
 import ctypes
 import json
 import os
@@ -50,8 +51,20 @@ KtDcSmall = _struct("KtDcSmall", DS_FIELDS, set("x h w3 b3 g1w g1b w1 b1 gram1 g
 KtGnMom = _struct("KtGnMom", GM_FIELDS, set("h out stats w b gram st_y".split()))
 KtFencRow = _struct("KtFencRow", FR_FIELDS, set(FR_FIELDS) - set("B Fin Fout T wc_ld w3_ld w1_ld wr_ld cin c".split()))
 
+MG_FIELDS = ("src src_bf16 H_src kept C stats gn_count gn_w gn_b skip skip_bf16 H_skip C_skip P out out_bf16 H_out W NI "
+             "proj_w proj_b fast_gelu").split()
+LR_FIELDS = ("steps Z Zs z_bf16 z_taps Hs Hk Hd W Co P NI bias stats gn_w gn_b fast_gelu skip skip_bf16 H_skip C_skip out "
+             "out_bf16 S Wt w_ld Ci z4 gram gq").split()
+DL_FIELDS = ("in_ in_bf16 NI P H W T fold skip skip_bf16 H_skip C_skip out g g_bf16 Hg stats gn_count gn_w gn_b fast_gelu "
+             "skip2 skip2_bf16 H_skip2 C_skip2").split()
+KtMerge = _struct("KtMerge", MG_FIELDS, set("src stats gn_w gn_b skip out proj_w proj_b".split()))
+KtLowRank = _struct("KtLowRank", LR_FIELDS,
+                    set("steps Z Zs bias stats gn_w gn_b skip out S Wt z4 gram gq".split()))
+KtDecLast = _struct("KtDecLast", DL_FIELDS, set("in_ fold skip out g stats gn_w gn_b skip2".split()))
+_DEC = (("merge", KtMerge), ("lowrank", KtLowRank), ("declast", KtDecLast))
+
 _NEW = (("conv3", KtConv3), ("apply", KtApply), ("dcsmall", KtDcSmall), ("gnmom", KtGnMom), ("fencrow", KtFencRow))
-for _n in ("gemm", "attn", "ln", "convt4") + tuple(n for n, _ in _NEW):
+for _n in ("gemm", "attn", "ln", "convt4", "lrstep") + tuple(n for n, _ in _NEW + _DEC):
     getattr(lib, "kt_sizeof_" + _n).restype = ctypes.c_int64
 lib.kt_sk_bytes.restype = ctypes.c_int64
 lib.kt_sk_resident.restype = ctypes.c_int64
@@ -84,6 +97,35 @@ lib.kt_host_f2bf.argtypes = [_I]
 lib.kt_conv1x1_moments.restype = None
 lib.kt_conv1x1_moments.argtypes = [_P, _P, _I, _I, _I, _P]
 
+# ---- the decoder kernels and the folded last level ----
+for _n in ("dec_merge", "fdec_lr_stats", "fdec_lr_merge", "fdec1_gram", "fdec_last", "tdec_last", "fdec_tail",
+           "tdec_tail"):
+    getattr(lib, "kt_" + _n).argtypes = [_P, _P]
+lib.kt_fdec1_gram_supported.argtypes = [_P]
+lib.kt_tdec_tail_supported.argtypes = [_P]
+lib.kt_fdec_lr_steps.argtypes = [_P, _I, _I, _I, _I, _P]
+for _n in ("fl_dc", "ft_dc", "tl_in", "tt_rows", "dm_run", "merge_maxp", "g_wb", "fdec1_gram_blocks",
+           "fdec1_gram_q_doubles"):
+    getattr(lib, "kt_" + _n).restype = _I
+    getattr(lib, "kt_" + _n).argtypes = []
+lib.kt_fdec1_gram_floats.restype = _I
+lib.kt_fdec1_gram_floats.argtypes = [_I, _I]
+lib.kt_dec_last_fold.restype = _I
+lib.kt_dec_last_fold.argtypes = [_P, _P, _P, _P, _I, _P]
+# one LrStep of kernels.h (fdec_lr_steps_launch writes Hd + 1 of them)
+LRSTEP = np.dtype([("lz", "<f4"), ("lk", "<f4"), ("lj", "<f4"), ("zk", "<u4"), ("jj", "<u4"), ("flags", "<u4"),
+                   ("pad", "<u4", (2,))])
+
+
+def dec_last_fold(w, b, P, pb, br):
+    """ctx.h dec_last_fold: ConvT weight [48][4][8], bias [4], projection [2][4], bias [2], branch -> float32 fold"""
+    a = [np.ascontiguousarray(v, dtype=np.float32) for v in (w, b, P, pb)]
+    assert a[0].shape == (48, 4, 8) and a[1].shape == (4,) and a[2].shape == (2, 4) and a[3].shape == (2,)
+    n = lib.kt_dec_last_fold(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, br, None)
+    out = np.zeros(n, dtype=np.float32)
+    lib.kt_dec_last_fold(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, br, out.ctypes.data)
+    return out
+
 
 def conv1x1_moments(w, b, round_bf16):
     """ctx.h conv1x1_moments of W [N][H], b [N] -> float32 [H*H + 2H + 2]"""
@@ -97,7 +139,7 @@ def conv1x1_moments(w, b, round_bf16):
 
 def sizes_match():
     return {n: (getattr(lib, "kt_sizeof_" + n)(), ctypes.sizeof(s))
-            for n, s in (("gemm", KtGemm), ("attn", KtAttn), ("ln", KtLn), ("convt4", KtConvT4)) + _NEW}
+            for n, s in (("gemm", KtGemm), ("attn", KtAttn), ("ln", KtLn), ("convt4", KtConvT4)) + _NEW + _DEC}
 
 
 GEMM_DEFAULTS = dict(nb=1, H_in=1, W=1, a_cs=1, a_bs=-1, a_hs=-1, ntaps=1, in_stride=1, dil=1, H_out=1, H_out_total=1,
@@ -176,6 +218,7 @@ def sync():
 REPORT = os.path.join(os.environ.get("ATHD_OUT") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                                  "bench_out"), "kernel_parity_report.json")
 DCONV_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_dconv_report.json")
+DEC_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_dec_report.json")
 _reports = {}
 
 
