@@ -21,6 +21,11 @@ struct AttnDesc {
     float scale = 0.125f;
 };
 
+// mode 1 (bf16): attn32_kernel, -3 for operands it does not take; mode 0 (f32 parity): attn_kernel<0>
 int attn_launch(const AttnDesc& d, int mode, hipStream_t s);
+
+// Ping-pong form attn_pp_kernel<prio> (attn_pp.hip: tools/libkbench.so and libathd_ktest.so only, not in libathd.so);
+// prio 0, 1 or 2.  -2 for operands attn32_kernel does not take.
+int attn_pp_launch(const AttnDesc& d, int prio, hipStream_t s);
 
 }  // namespace athd

@@ -125,7 +125,7 @@ void kt_sk_plan(const KtGemm* k, int64_t* out) {
     out[0] = p.full; out[1] = p.tail; out[2] = p.S;
 }
 
-int kt_attn(const KtAttn* k, int mode, void* stream) {
+static AttnDesc to_attn_desc(const KtAttn* k) {
     AttnDesc a;
     a.Q = k->Q; a.q_bf16 = (int)k->q_bf16; a.q_bs = k->q_bs; a.q_ld = (int)k->q_ld; a.q_off = (int)k->q_off;
     a.K = k->K; a.k_bf16 = (int)k->k_bf16; a.k_bs = k->k_bs; a.k_ld = (int)k->k_ld; a.k_off = (int)k->k_off;
@@ -134,8 +134,12 @@ int kt_attn(const KtAttn* k, int mode, void* stream) {
     a.nb = (int)k->nb; a.Nq = (int)k->Nq; a.Nk = (int)k->Nk; a.heads = (int)k->heads;
     const uint32_t bits = (uint32_t)k->scale_bits;
     memcpy(&a.scale, &bits, 4);
-    return attn_launch(a, mode, (hipStream_t)stream);
+    return a;
 }
+
+int kt_attn(const KtAttn* k, int mode, void* stream) { return attn_launch(to_attn_desc(k), mode, (hipStream_t)stream); }
+// the ping-pong form attn_pp_kernel<prio> (attn_pp.hip, linked into this library only)
+int kt_attn_pp(const KtAttn* k, int prio, void* stream) { return attn_pp_launch(to_attn_desc(k), prio, (hipStream_t)stream); }
 
 int kt_layernorm(const KtLn* k, void* stream) {
     LnDesc l;

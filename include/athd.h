@@ -168,7 +168,7 @@ int athd_spectrogram_db(const float* wav, int channels, int64_t T, float* out, v
 
 /* Kernel timing (measurement aid for bench.py; not part of the reference interface).  Between
  * athd_profile_start and athd_profile_stop every launch of kernel `kernel` (its rocprofv3 symbol without
- * "void athd::", the argument list and 'u' suffixes, e.g. "attn_bf16_kernel"; NULL or "" = all kernels) made
+ * "void athd::", the argument list and 'u' suffixes, e.g. "attn_kernel<0>"; NULL or "" = all kernels) made
  * by this context's forwards is bracketed by HIP events on the launch stream.  athd_profile_stop synchronises
  * those events and aggregates per kernel: launches, summed event time, summed ALGORITHMIC flops and bytes.
  * kernel = "@section": every kernel, aggregated per forward section ("encoder", "transformer", "decoder").

@@ -74,6 +74,7 @@ lib.kt_sk_plan.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.kt_gemm.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
 lib.kt_gemm_route.argtypes = [ctypes.c_void_p, ctypes.c_int]
 lib.kt_attn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+lib.kt_attn_pp.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
 lib.kt_layernorm.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.kt_convt4.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 _P, _I = ctypes.c_void_p, ctypes.c_int64

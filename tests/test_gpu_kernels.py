@@ -1,5 +1,6 @@
 """Kernel-level parity: the launchers of csrc/gemm.h, attn.h and kernels.h against the float64 references and derived
-tolerances of tests/kernel_refs.py, called through libathd_ktest.so (the exact objects libathd.so ships).
+tolerances of tests/kernel_refs.py, called through libathd_ktest.so (the exact objects libathd.so ships, plus the
+ping-pong attention kernel of csrc/attn_pp.hip, which is built into the test library only).
 
 Common rules: every device buffer has guard bands (operands: a large finite value, outputs: a sentinel) of at least a
 tile of rows, untouched output elements must keep their sentinel, batches and heads are scaled by different powers
@@ -59,7 +60,10 @@ def _check_output(buf, init, idx, R, tol, bf16):
 
 # =====================================================================================================  attention
 ATTN_PAIRS = [(1, 1), (33, 1), (31, 8), (127, 63), (128, 64), (129, 65), (128, 127), (257, 129), (257, 200), (1, 64),
-              (16, 65), (64, 128), (65, 192), (130, 193), (200, 257), (255, 130), (256, 64), (257, 66)]
+              (16, 65), (64, 128), (65, 192), (130, 193), (200, 257), (255, 130), (256, 64), (257, 66),
+              # many key tiles (attn_pp_kernel's 4-slot rings wrap twice): 10 tiles with a 1-key tail and two 256-query
+              # blocks; 8 full tiles, no tail, a third 256-query block holding a single query
+              (300, 577), (513, 512)]
 NB, HEADS = 2, 8
 
 
@@ -80,8 +84,8 @@ def _attn_inputs(rng, Nq, Nk, mult, place, bf16):
     return kr.bf16_round(q), kr.bf16_round(k), kr.bf16_round(v)
 
 
-def _attn_run(kt, q, k, v, layout, bf16, mode):
-    """-> (O [nb][H][Nq][64] float64, O bits/raw)"""
+def _attn_run(kt, q, k, v, layout, bf16, mode, pp_prio=None):
+    """-> (O [nb][H][Nq][64] float64, O bits/raw); pp_prio: attn_pp_kernel<pp_prio> instead of attn_launch(mode)"""
     Nq, Nk = q.shape[2], k.shape[2]
     tok = lambda x: np.transpose(x, (0, 2, 1, 3)).reshape(NB, x.shape[2], 512)     # [nb][N][512]
     big = 3.0e38
@@ -108,7 +112,7 @@ def _attn_run(kt, q, k, v, layout, bf16, mode):
     d = kt.fill(kt.KtAttn, q_bf16=b, k_bf16=b, v_bf16=b, o_bf16=b, O=bo.ptr, o_bs=Nq * 512, o_ld=512, nb=NB, Nq=Nq,
                 Nk=Nk, heads=HEADS, scale_bits=kt.f32_bits(LN2 if bf16 else 0.125), **lay)
     import ctypes
-    rc = kt.lib.kt_attn(ctypes.byref(d), mode, None)
+    rc = kt.lib.kt_attn(ctypes.byref(d), mode, None) if pp_prio is None else kt.lib.kt_attn_pp(ctypes.byref(d), pp_prio, None)
     kt.sync()
     assert rc == 0, rc
     raw, bands = bo.host()
@@ -124,30 +128,22 @@ ATTN_VARIANTS = [(1, "rand"), (36, "rand"), (400, "rand"), (1, "first"), (36, "f
 @pytest.mark.parametrize("layout", ["qkv", "q_kv"])
 @pytest.mark.parametrize("Nq,Nk", ATTN_PAIRS)
 def test_attn_bf16(kt, Nq, Nk, layout):
-    """attn32_kernel<3,2,true> (ATHD_ATTN_PP unset) within tol = 4u (P|V|) + 2u |R|, and attn_pp_kernel
-    (ATHD_ATTN_PP = 1, 2, 3) bit-identical to it."""
+    """attn32_kernel<3,2,true> within tol = 4u (P|V|) + 2u |R|, and attn_pp_kernel<1>, <0> and <2> (kt_attn_pp)
+    bit-identical to it."""
     rng = np.random.default_rng(1000 * Nq + Nk)
     worst = 0.0
-    old = os.environ.pop("ATHD_ATTN_PP", None)
-    try:
-        for mult, place in ATTN_VARIANTS:
-            q, k, v = _attn_inputs(rng, Nq, Nk, mult, place, True)
-            R, tol = kr.attn_ref(q, k, v, LN2, 1)
-            if place == "kzero":
-                assert np.abs(R - v.mean(axis=2, keepdims=True)).max() < 1e-12 * np.abs(v).max()
-            o0, raw0 = _attn_run(kt, q, k, v, layout, True, 1)
-            r = _ratio(o0, R, tol)
-            print("attn bf16 Nq=%d Nk=%d %s x%d %s: err/tol %.3f" % (Nq, Nk, layout, mult, place, r))
-            worst = max(worst, r)
-            for pp in ("1", "2", "3"):
-                os.environ["ATHD_ATTN_PP"] = pp
-                _, raw = _attn_run(kt, q, k, v, layout, True, 1)
-                del os.environ["ATHD_ATTN_PP"]
-                assert np.array_equal(raw, raw0), "ATHD_ATTN_PP=%s differs from attn32_kernel (x%d %s)" % (pp, mult, place)
-    finally:
-        os.environ.pop("ATHD_ATTN_PP", None)
-        if old is not None:
-            os.environ["ATHD_ATTN_PP"] = old
+    for mult, place in ATTN_VARIANTS:
+        q, k, v = _attn_inputs(rng, Nq, Nk, mult, place, True)
+        R, tol = kr.attn_ref(q, k, v, LN2, 1)
+        if place == "kzero":
+            assert np.abs(R - v.mean(axis=2, keepdims=True)).max() < 1e-12 * np.abs(v).max()
+        o0, raw0 = _attn_run(kt, q, k, v, layout, True, 1)
+        r = _ratio(o0, R, tol)
+        print("attn bf16 Nq=%d Nk=%d %s x%d %s: err/tol %.3f" % (Nq, Nk, layout, mult, place, r))
+        worst = max(worst, r)
+        for prio in (1, 0, 2):
+            _, raw = _attn_run(kt, q, k, v, layout, True, 1, pp_prio=prio)
+            assert np.array_equal(raw, raw0), "attn_pp_kernel<%d> differs from attn32_kernel (x%d %s)" % (prio, mult, place)
     kt.record("attn_bf16[%d,%d,%s]" % (Nq, Nk, layout), err_over_tol=worst, pp_bit_identical=True)
     assert worst <= 1.0
 
@@ -171,18 +167,20 @@ def test_attn_f32(kt, Nq, Nk, layout):
 
 def test_attn_refuses_wide_pitch(kt):
     """a K / V row pitch of 2^23 elements or more does not fit the LDS-DMA staging's 24-bit offsets: bf16 mode refuses
-    it (no launch) instead of computing with a wrapped pitch"""
+    it (no launch) instead of computing with a wrapped pitch, and so does every form of attn_pp_kernel"""
     import ctypes
     bo = kt.Buf(np.full(512, kt.BF16_SENTINEL_BITS, dtype=np.uint16), "bf16", 512, output=True)
     bq = kt.Buf(np.zeros(1536, dtype=np.uint16), "bf16", 1536)
     d = kt.fill(kt.KtAttn, q_bf16=1, k_bf16=1, v_bf16=1, o_bf16=1, O=bo.ptr, o_bs=512, o_ld=512, nb=1, Nq=1, Nk=1,
                 heads=8, scale_bits=kt.f32_bits(LN2), Q=bq.ptr, q_ld=1536, K=bq.ptr, k_ld=1 << 23, k_off=512, V=bq.ptr,
                 v_ld=1 << 23, v_off=1024)
-    rc = kt.lib.kt_attn(ctypes.byref(d), 1, None)
-    kt.sync()
-    assert rc != 0
-    raw, bands = bo.host()
-    assert bands and (raw == kt.BF16_SENTINEL_BITS).all()
+    for launch in (lambda: kt.lib.kt_attn(ctypes.byref(d), 1, None),) + tuple(
+            (lambda p=p: kt.lib.kt_attn_pp(ctypes.byref(d), p, None)) for p in (1, 0, 2)):
+        rc = launch()
+        kt.sync()
+        assert rc != 0
+        raw, bands = bo.host()
+        assert bands and (raw == kt.BF16_SENTINEL_BITS).all()
 
 
 # =====================================================================================================  GEMM

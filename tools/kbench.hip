@@ -6,9 +6,6 @@
 #include <hip/hip_runtime.h>
 
 using namespace athd;
-namespace athd {
-extern int g_attn_variant;
-}
 
 extern "C" {
 // out[M][N] = act(A[M][K] @ W[N][Kp]^T + bias); variant 1 = v1 kernel, 2 = v2 kernel
@@ -70,16 +67,18 @@ int kb_convt_quad(int variant, int kskip, const void* A, const void* W, const fl
     if (kskip == 3) d.stats = nullptr;      // probe: no statistics
     return gemm3_variant_launch(d, (hipStream_t)stream, variant);
 }
-// variant: 0 = attn32<2>, 1 = attn_bf16 (16x16x32), 2 = attn32<3>; prescaled = Q already x ATTN_Q_PRESCALE
+// variant: 0 = attn_launch (attn32_kernel<3,2,true>), 1 / 2 / 3 = attn_pp_kernel<1> / <0> / <2>; prescaled = Q already
+// x ATTN_Q_PRESCALE (both kernels refuse anything else)
 int kb_attn(int variant, int prescaled, const void* qkv, int nb, int N, void* out, void* stream) {
-    g_attn_variant = variant;
+    if (variant < 0 || variant > 3) return -1;
     AttnDesc a;
     a.nb = nb; a.Nq = N; a.Nk = N; a.heads = 8; a.scale = prescaled ? ATTN_SCALE_PRESCALED : 0.125f;
     a.Q = qkv; a.q_bf16 = 1; a.q_bs = (int64_t)N * 1536; a.q_ld = 1536; a.q_off = 0;
     a.K = qkv; a.k_bf16 = 1; a.k_bs = (int64_t)N * 1536; a.k_ld = 1536; a.k_off = 512;
     a.V = qkv; a.v_bf16 = 1; a.v_bs = (int64_t)N * 1536; a.v_ld = 1536; a.v_off = 1024;
     a.O = out; a.o_bf16 = 1; a.o_bs = (int64_t)N * 512; a.o_ld = 512;
-    return attn_launch(a, 1, (hipStream_t)stream);
+    static const int pp_prio[4] = {-1, 1, 0, 2};
+    return variant == 0 ? attn_launch(a, 1, (hipStream_t)stream) : attn_pp_launch(a, pp_prio[variant], (hipStream_t)stream);
 }
 }
 
