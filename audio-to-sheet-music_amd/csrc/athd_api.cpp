@@ -196,7 +196,7 @@ int athd_finalize(athd_ctx* c) {
             e.cout = C;
             e.conv = c->conv_gemm(p + ".conv.weight", p + ".conv.bias", C, e.cin, 8);
             e.rewrite = c->conv_gemm(p + ".rewrite.weight", p + ".rewrite.bias", 2 * C, C, 1, true);
-            if (c->mode == 1 && (C == 48 || C == 96)) {
+            if (dconv_bf16(c->mode) && dconv_narrow(C)) {
                 // the K order of the fused DConv apply (ctx.h dconv_rewrite_perm)
                 const auto& w = c->W(p + ".rewrite.weight").v;     // [2C][C]
                 const int K2 = (C + 31) / 32 * 32;
@@ -228,7 +228,7 @@ int athd_finalize(athd_ctx* c) {
                 e.dc.g2w[d] = c->up_f32(athd_ctx::glu_order(c->W(q + ".4.weight").v));
                 e.dc.g2b[d] = c->up_f32(athd_ctx::glu_order(c->W(q + ".4.bias").v));
                 e.dc.scale[d] = c->up_key(q + ".6.scale");
-                if (C <= 96) {
+                if (dconv_narrow(C)) {
                     const auto& w3 = c->W(q + ".0.weight").v;      // [H][C][3] -> [H][tap*C + c]
                     const int H = C / 8;
                     std::vector<float> t3((size_t)H * 3 * C);
@@ -236,19 +236,19 @@ int athd_finalize(athd_ctx* c) {
                         for (int ci = 0; ci < C; ++ci)
                             for (int t = 0; t < 3; ++t) t3[((size_t)j * 3 + t) * C + ci] = w3[((size_t)j * C + ci) * 3 + t];
                     e.dc.w3f[d] = c->up_f32(t3);
-                    if (c->mode == 1) {
+                    if (dconv_bf16(c->mode)) {
                         std::vector<float> t16((size_t)16 * 3 * C, 0.f);
                         std::copy(t3.begin(), t3.end(), t16.begin());
                         e.dc.c3p[d] = c->up_gemm(t16, 16, 3 * C, {});
                     }
                     e.dc.w1f[d] = c->up_key(q + ".3.weight");        // [2C][H][1] == [2C][H]
                     e.dc.gram1[d] = c->up_f32(conv1x1_moments(c->W(q + ".3.weight").v, c->W(q + ".3.bias").v, 2 * C, H, false));
-                    if (c->mode == 1)
+                    if (dconv_bf16(c->mode))
                         e.dc.gram1b[d] = c->up_f32(conv1x1_moments(c->W(q + ".3.weight").v, c->W(q + ".3.bias").v, 2 * C, H, true));
                     e.dc.b1f[d] = c->up_key(q + ".3.bias");
                     e.dc.g2wf[d] = c->up_key(q + ".4.weight");
                     e.dc.g2bf[d] = c->up_key(q + ".4.bias");
-                } else if (c->mode == 1) {      // wide levels: the 1x1's statistics from its moments (gn_gelu_mom)
+                } else if (dconv_bf16(c->mode)) {      // wide levels: the 1x1's statistics from its moments (gn_gelu_mom)
                     e.dc.gram1b[d] = c->up_f32(conv1x1_moments(c->W(q + ".3.weight").v, c->W(q + ".3.bias").v, 2 * C, C / 8, true));
                 }
             }

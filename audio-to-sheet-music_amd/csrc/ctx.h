@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "gemm.h"
 #include "prof.h"
 
 namespace athd {
@@ -30,7 +31,7 @@ struct DConvW {
     // 1x1 [2C][H], its bias and GroupNorm affine
     float *w3f[2] = {nullptr, nullptr}, *w1f[2] = {nullptr, nullptr}, *b1f[2] = {nullptr, nullptr};
     float *g2wf[2] = {nullptr, nullptr}, *g2bf[2] = {nullptr, nullptr};
-    // moments of the 1x1 conv for its GroupNorm statistics (dconv.hip c1stat): G = W^T W [H][H], v = W^T b [H],
+    // moments of the 1x1 conv for its GroupNorm statistics (dconv_small.hip c1stat): G = W^T W [H][H], v = W^T b [H],
     // ws = W^T 1 [H], sum b, sum b^2 (so sum_n y_n and sum_n y_n^2 of y = W h + b come from h alone)
     float* gram1[2] = {nullptr, nullptr};
     float* gram1b[2] = {nullptr, nullptr};   // the same from the bf16-rounded weights (fenc_row.hip, bf16 mode)
@@ -228,7 +229,7 @@ struct athd_ctx {
         GemmW g;
         g.N = N;
         g.K = K;
-        g.Kp = (int)rup(K, 64);
+        g.Kp = gemm_kp(K);
         const int Nalloc = (int)rup(N, 256);
         if (mode == 1) {
             std::vector<uint16_t> p((size_t)Nalloc * g.Kp, 0);

@@ -1,14 +1,6 @@
-// DConv (demucs residual dilated-conv branch) for the narrow levels (C = 48, 96; hidden
-// H = C/8 = 6, 12).  These layers are HBM-bound with K or N far below an MFMA tile, so they run as VALU kernels.
-// x is [nb][L][C] in f32 (parity mode) or bf16 (throughput mode); h is [nb][L][H] f32.  One layer = 3 passes
-// (each GroupNorm needs complete statistics before it can be applied):
-//   c3:     h = b + W3 * x[t - dil], x[t], x[t + dil]          + GroupNorm statistics of h per group
-//   c1stat: y = b1 + W1 * GELU(GN(h))   (2C outputs, never stored)  -> GroupNorm statistics of y per group
-//   c1app:  x += scale * GLU(GN(y))     (y recomputed: K = H is tiny)
-// A "group" is the GroupNorm(1) sample: one nb row of L positions (freq rows (b,f) along time, or time samples).
-// Access pattern: c3 stages its x tile (+ dilation halo) in LDS with 16-B coalesced loads; the 1x1 passes map a
-// lane to one position.  Every weight is read at a wave-uniform address (scalar loads, SGPR operands of the FMAs:
-// no LDS traffic for weights).  Per-group GroupNorm parameters are finalised once per block into LDS.
+// DConv (demucs residual dilated-conv branch), bf16 mode: the three passes of one layer with
+// their weights resident in LDS (apply, conv3, gn_gelu_mom between them; C = 48, 96, 192, 384), and dconv_plan, which
+// decides a level's launches from the launchers' shape predicates.  (The narrow levels' VALU layer: dconv_small.hip.)
 #include <algorithm>
 
 #include "common.h"
@@ -17,295 +9,6 @@
 
 namespace athd {
 
-template <typename TS> struct XS;
-template <> struct XS<float> {
-    static ATHD_DEV float ld(const float* p, int64_t i) { return p[i]; }
-};
-template <> struct XS<bf16_t> {
-    static ATHD_DEV float ld(const bf16_t* p, int64_t i) { return bf2f(p[i]); }
-};
-
-// 16 B of x -> EPC floats
-template <typename TS>
-ATHD_DEV void unpack16(const uint4 q, float* v) {
-    if constexpr (sizeof(TS) == 2) {
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __uint_as_float(w[i] << 16);
-            v[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
-        }
-    } else {
-        v[0] = __uint_as_float(q.x); v[1] = __uint_as_float(q.y); v[2] = __uint_as_float(q.z); v[3] = __uint_as_float(q.w);
-    }
-}
-
-// Block-level {sum, sumsq} per group.  Blocks cover <= 256 consecutive positions, so with L >= 256 a block spans
-// at most two groups (g0 and g0 + 1).  Shorter rows fall back to per-thread atomics.
-ATHD_DEV void group_stats_add(double* __restrict__ st, int64_t p0, int64_t p, bool valid, int64_t L, float s1, float s2,
-                              double* sh) {
-    if (L < 256) {
-        if (valid) {
-            atomicAdd(&st[2 * (p / L)], (double)s1);
-            atomicAdd(&st[2 * (p / L) + 1], (double)s2);
-        }
-        return;
-    }
-    const int64_t g0 = p0 / L;
-    const bool second = valid && (p / L) != g0;
-    double a0 = (valid && !second) ? s1 : 0.0, b0 = (valid && !second) ? s2 : 0.0;
-    double a1 = second ? s1 : 0.0, b1 = second ? s2 : 0.0;
-    a0 = wave_sum_d(a0); b0 = wave_sum_d(b0); a1 = wave_sum_d(a1); b1 = wave_sum_d(b1);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[4 * w] = a0; sh[4 * w + 1] = b0; sh[4 * w + 2] = a1; sh[4 * w + 3] = b1; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        double v = 0.0;
-        for (int i = 0; i < 4; ++i) v += sh[4 * i + threadIdx.x];
-        const int64_t g = g0 + (threadIdx.x >= 2 ? 1 : 0);
-        if (v != 0.0) atomicAdd(&st[2 * g + (threadIdx.x & 1)], v);
-    }
-}
-
-ATHD_DEV void gn_mr(const double* st, int64_t g, double cnt, float& mean, float& rstd) {
-    const double mm = st[2 * g] / cnt;
-    double var = st[2 * g + 1] / cnt - mm * mm;
-    if (var < 0) var = 0;
-    mean = (float)mm;
-    rstd = (float)(1.0 / sqrt(var + 1e-5));
-}
-
-// ---- c3: TILE positions per block, TPP = 256 / TILE threads per position, each computing H / TPP outputs
-template <int C, typename TS>
-__global__ __launch_bounds__(256) void dconv_c3_kernel(const TS* __restrict__ x, int64_t nb, int64_t L, int dil,
-                                                       const float* __restrict__ W, const float* __restrict__ bias,
-                                                       float* __restrict__ h, double* __restrict__ st) {
-    constexpr int H = C / 8, K = 3 * C, HALO = 2;
-    constexpr int TILE = sizeof(TS) == 2 ? 256 : 128;
-    constexpr int TPP = 256 / TILE, HJ = H / TPP;
-    constexpr int ROWS = TILE + 2 * HALO;
-    constexpr int EPC = 16 / sizeof(TS);                    // elements per 16-B chunk
-    constexpr int CPR = C / EPC;                             // chunks per row
-    __shared__ __attribute__((aligned(16))) TS xs[ROWS * C];
-    __shared__ double sh[16];
-    const int64_t P = nb * L;
-    const int64_t p0 = (int64_t)blockIdx.x * TILE;
-    for (int i = threadIdx.x; i < ROWS * CPR; i += 256) {
-        const int r = i / CPR, ch = i - r * CPR;
-        const int64_t pp = p0 - HALO + r;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (pp >= 0 && pp < P) v = *reinterpret_cast<const uint4*>(x + pp * C + ch * EPC);
-        *reinterpret_cast<uint4*>(&xs[r * C + ch * EPC]) = v;
-    }
-    __syncthreads();
-    const int lp = threadIdx.x / TPP, sub = threadIdx.x % TPP;
-    const int64_t p = p0 + lp;
-    const bool valid = p < P;
-    float s1 = 0.f, s2 = 0.f;
-    if (valid) {
-        const int64_t t = p % L;
-        float acc[HJ];
-#pragma unroll
-        for (int j = 0; j < HJ; ++j) acc[j] = bias[sub * HJ + j];
-#pragma unroll
-        for (int tap = 0; tap < 3; ++tap) {
-            const int64_t tt = t + (tap - 1) * dil;
-            if (tt < 0 || tt >= L) continue;                 // zero padding of the group row
-            const TS* xr = &xs[(lp + HALO + (tap - 1) * dil) * C];
-#pragma unroll 2
-            for (int c0 = 0; c0 < C; c0 += EPC) {
-                float v[EPC];
-                unpack16<TS>(*reinterpret_cast<const uint4*>(xr + c0), v);
-#pragma unroll
-                for (int e = 0; e < EPC; ++e)
-#pragma unroll
-                    for (int j = 0; j < HJ; ++j) acc[j] += W[(sub * HJ + j) * K + tap * C + c0 + e] * v[e];
-            }
-        }
-        float* hr = h + p * H + sub * HJ;
-#pragma unroll
-        for (int j = 0; j < HJ; ++j) {
-            hr[j] = acc[j];
-            s1 += acc[j];
-            s2 += acc[j] * acc[j];
-        }
-    }
-    group_stats_add(st, p0, p, valid, L, s1, s2, sh);
-}
-
-// GELU(GroupNorm(h)) of one position (the first GroupNorm of the layer, fused into both 1x1 passes)
-template <int H, bool FAST>
-ATHD_DEV void load_hg(const float* __restrict__ h, int64_t p, float mean, float rstd, const float* g1w, const float* g1b,
-                      float* hv) {
-#pragma unroll
-    for (int j = 0; j < H; ++j) hv[j] = gelu<FAST>((h[p * H + j] - mean) * rstd * g1w[j] + g1b[j]);
-}
-
-// GroupNorm (mean, rstd) of the groups [g_first, g_first + n) a block touches, into LDS (n <= GN_TAB); the caller
-// synchronises.  Blocks touching more groups (very short rows) compute per thread.
-constexpr int GN_TAB = 8;
-ATHD_DEV void gn_table(const double* st, double cnt, int64_t g_first, int64_t n, float* tm, float* tr) {
-    if (n <= GN_TAB && (int64_t)threadIdx.x < n) gn_mr(st, g_first + threadIdx.x, cnt, tm[threadIdx.x], tr[threadIdx.x]);
-}
-ATHD_DEV void gn_lookup(const double* st, double cnt, int64_t g, int64_t g_first, int64_t n, const float* tm,
-                        const float* tr, float& mean, float& rstd) {
-    if (n <= GN_TAB) {
-        mean = tm[g - g_first];
-        rstd = tr[g - g_first];
-    } else {
-        gn_mr(st, g, cnt, mean, rstd);
-    }
-}
-
-// ---- c1stat: one thread per position.  y = W h + b (2C channels) only feeds the GroupNorm statistics, and
-// sum_n y_n = sum b + ws.h, sum_n y_n^2 = sum b^2 + 2 v.h + h^T G h with the 1x1 conv's moments (G = W^T W, v = W^T b,
-// ws = W^T 1: ctx.h DConvW::gram1, computed in fp64 at pack time): H^2 + 3H FMAs per position instead of 2 x 2C x H
-template <int C, bool FAST>
-__global__ __launch_bounds__(256) void dconv_c1_stats_kernel(const float* __restrict__ h, int64_t nb, int64_t L,
-                                                             const double* __restrict__ st_h,
-                                                             const float* __restrict__ g1w, const float* __restrict__ g1b,
-                                                             const float* __restrict__ gram, double* __restrict__ st_y) {
-    constexpr int H = C / 8;
-    __shared__ float tm[GN_TAB], tr[GN_TAB];
-    __shared__ double sh[16];
-    const int64_t P = nb * L;
-    const int64_t p0 = (int64_t)blockIdx.x * 256;
-    const int64_t gf = p0 / L, ng = (std::min<int64_t>(p0 + 255, P - 1)) / L - gf + 1;
-    gn_table(st_h, (double)L * H, gf, ng, tm, tr);
-    __syncthreads();
-    const int64_t p = p0 + threadIdx.x;
-    const bool valid = p < P;
-    float s1 = 0.f, s2 = 0.f;
-    if (valid) {
-        float mean, rstd;
-        gn_lookup(st_h, (double)L * H, p / L, gf, ng, tm, tr, mean, rstd);
-        float hv[H];
-        load_hg<H, FAST>(h, p, mean, rstd, g1w, g1b, hv);
-        const float* G = gram;
-        const float* v = gram + H * H;
-        const float* ws = v + H;
-        float q = 0.f, lv = 0.f, lw = 0.f;
-#pragma unroll
-        for (int j = 0; j < H; ++j) {
-            float t = 0.f;
-#pragma unroll
-            for (int k = 0; k < H; ++k) t += G[j * H + k] * hv[k];
-            q += hv[j] * t;
-            lv += v[j] * hv[j];
-            lw += ws[j] * hv[j];
-        }
-        s1 = ws[H] + lw;
-        s2 = ws[H + 1] + (2.f * lv + q);
-    }
-    group_stats_add(st_y, p0, p, valid, L, s1, s2, sh);
-}
-
-// ---- c1app: one thread per position, all C channels: x[p][:] += scale * GLU(GN(y)); every weight / affine read is
-// wave-uniform (scalar loads), x moves in 16-B chunks
-template <int C, typename TS, bool FAST>
-__global__ __launch_bounds__(256) void dconv_c1_apply_kernel(TS* __restrict__ x, const float* __restrict__ h, int64_t nb,
-                                                             int64_t L, const double* __restrict__ st_h,
-                                                             const float* __restrict__ g1w, const float* __restrict__ g1b,
-                                                             const float* __restrict__ W, const float* __restrict__ bias,
-                                                             const double* __restrict__ st_y,
-                                                             const float* __restrict__ g2w, const float* __restrict__ g2b,
-                                                             const float* __restrict__ scale) {
-    constexpr int H = C / 8, N = 2 * C;
-    constexpr int EPC = 16 / sizeof(TS);
-    __shared__ float tm1[GN_TAB], tr1[GN_TAB], tm2[GN_TAB], tr2[GN_TAB];
-    const int64_t P = nb * L;
-    const int64_t p0 = (int64_t)blockIdx.x * 256;
-    const int64_t gf = p0 / L, ng = (std::min<int64_t>(p0 + 255, P - 1)) / L - gf + 1;
-    gn_table(st_h, (double)L * H, gf, ng, tm1, tr1);
-    gn_table(st_y, (double)L * N, gf, ng, tm2, tr2);
-    __syncthreads();
-    const int64_t p = p0 + threadIdx.x;
-    if (p >= P) return;
-    const int64_t g = p / L;
-    float m1, r1, m2, r2;
-    gn_lookup(st_h, (double)L * H, g, gf, ng, tm1, tr1, m1, r1);
-    gn_lookup(st_y, (double)L * N, g, gf, ng, tm2, tr2, m2, r2);
-    float hv[H];
-    load_hg<H, FAST>(h, p, m1, r1, g1w, g1b, hv);
-    TS* xp = x + p * C;
-#pragma unroll 2
-    for (int c0 = 0; c0 < C; c0 += EPC) {
-        uint4 q = *reinterpret_cast<const uint4*>(xp + c0);
-        float e[EPC];
-        unpack16<TS>(q, e);
-#pragma unroll
-        for (int k = 0; k < EPC; ++k) {
-            const int c = c0 + k;
-            float a = bias[c], gt = bias[C + c];
-#pragma unroll
-            for (int j = 0; j < H; ++j) {
-                a += W[c * H + j] * hv[j];
-                gt += W[(C + c) * H + j] * hv[j];
-            }
-            a = (a - m2) * r2 * g2w[c] + g2b[c];
-            gt = (gt - m2) * r2 * g2w[C + c] + g2b[C + c];
-            const float o = scale[c] * (a * sigmoid<FAST>(gt));
-            e[k] += o;                                // rounded once below (pack2bf: RNE, as f2bf)
-        }
-        if constexpr (sizeof(TS) == 2)
-            q = make_uint4(pack2bf(e[0], e[1]), pack2bf(e[2], e[3]), pack2bf(e[4], e[5]), pack2bf(e[6], e[7]));
-        else
-            q = make_uint4(__float_as_uint(e[0]), __float_as_uint(e[1]), __float_as_uint(e[2]), __float_as_uint(e[3]));
-        *reinterpret_cast<uint4*>(xp + c0) = q;
-    }
-}
-
-template <int C, typename TS, bool FAST>
-static void dconv_small_t(void* x, float* h, int64_t nb, int64_t L, int dil, const float* w3, const float* b3,
-                          const float* g1w, const float* g1b, const float* w1, const float* b1, const float* gram1,
-                          const float* g2w, const float* g2b, const float* scale, double* st_h, double* st_y,
-                          hipStream_t s) {
-    constexpr int H = C / 8, TILE = sizeof(TS) == 2 ? 256 : 128;
-    const int64_t P = nb * L;
-    const double px = (double)P;
-    const double xb = (double)sizeof(TS);
-    const char* tn = sizeof(TS) == 2 ? "unsignedshort" : "float";   // (rocprofv3 symbol spelling)
-    {
-        KScope ks(s);
-        if (ks.on()) ks.begin(klabel("dconv_c3_kernel<%d,%s>", C, tn), 2.0 * px * H * 3 * C, px * (C * xb + H * 4));
-        hipLaunchKernelGGL((dconv_c3_kernel<C, TS>), dim3((unsigned)((P + TILE - 1) / TILE)), dim3(256), 0, s,
-                           (const TS*)x, nb, L, dil, w3, b3, h, st_h);
-    }
-    {
-        KScope ks(s);
-        if (ks.on()) ks.begin(klabel("dconv_c1_stats_kernel<%d,%s>", C, FAST ? "true" : "false"), 2.0 * px * (H * H + 3 * H), px * H * 4);
-        hipLaunchKernelGGL((dconv_c1_stats_kernel<C, FAST>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, h, nb,
-                           L, st_h, g1w, g1b, gram1, st_y);
-    }
-    {
-        KScope ks(s);
-        if (ks.on()) ks.begin(klabel("dconv_c1_apply_kernel<%d,%s,%s>", C, tn, FAST ? "true" : "false"), 2.0 * px * 2 * C * H, px * (H * 4 + 2 * C * xb));
-        hipLaunchKernelGGL((dconv_c1_apply_kernel<C, TS, FAST>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s,
-                           (TS*)x, h, nb, L, st_h, g1w, g1b, w1, b1, st_y, g2w, g2b, scale);
-    }
-}
-
-int dconv_small_launch(void* x, int x_bf16, float* h, int64_t nb, int64_t L, int C, int dil, const float* w3,
-                       const float* b3, const float* g1w, const float* g1b, const float* w1, const float* b1,
-                       const float* gram1, const float* g2w, const float* g2b, const float* scale, double* st_h,
-                       double* st_y, hipStream_t s, bool fast) {
-    if (dil < 1 || dil > 2 || !gram1) return -2;
-#define ATHD_DC(CC, TS, FA) \
-    dconv_small_t<CC, TS, FA>(x, h, nb, L, dil, w3, b3, g1w, g1b, w1, b1, gram1, g2w, g2b, scale, st_h, st_y, s)
-    if (C == 48) {
-        if (x_bf16) { if (fast) ATHD_DC(48, bf16_t, true); else ATHD_DC(48, bf16_t, false); }
-        else { if (fast) ATHD_DC(48, float, true); else ATHD_DC(48, float, false); }
-    } else if (C == 96) {
-        if (x_bf16) { if (fast) ATHD_DC(96, bf16_t, true); else ATHD_DC(96, bf16_t, false); }
-        else { if (fast) ATHD_DC(96, float, true); else ATHD_DC(96, float, false); }
-    } else {
-        return -2;
-    }
-#undef ATHD_DC
-    return (int)hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // Wide levels (C = 192, 384; bf16 mode): the DConv 1x1 apply  x += LayerScale(GLU(GN(W1 hb + b1)))  as a weights-
 // resident MFMA pass (the pattern of convt4.hip) instead of a tiled GEMM: K = H = C/8 (24, 48) is one or two 32-wide
 // K-steps, so the tiled GEMM (gemm3 / gemm5, one K-tile per 256-row tile) was all prologue and epilogue at ~7 GB/s
@@ -670,55 +373,302 @@ __global__ __launch_bounds__(NW * 64) void dconv_conv3_kernel(const DcConv3 d) {
     flush();
 }
 
+// Wide DConv levels (H = C/8 = 24, 48; bf16 mode): gn_gelu_bf16_kernel's output plus the GroupNorm statistics of the
+// following 1x1 conv's 2C outputs from its moments (ctx.h conv1x1_moments on the bf16-rounded weights: G = W^T W,
+// v = W^T b, u = W^T 1, sum b, sum b^2), so no separate statistics GEMM pass over the 1x1 (forward.cpp dconv):
+//   sum_n y_n = sum b + u.x,   sum_n y_n^2 = sum b^2 + 2 v.x + x^T G x,   x = the bf16 GELU(GN(h)) row the GEMM reads.
+// One lane per position (row of H channels); groups of L >= 64 positions, so a wave spans at most two groups (its
+// sums go to the first active lane's group and, for lanes past a boundary, to the last lane's group).
+constexpr int GN_MOM_RMAX = 4;
+
+template <int H, bool MULTI>
+__global__ __launch_bounds__(256) void gn_gelu_mom_kernel(const float* __restrict__ h, bf16_t* __restrict__ out,
+                                                          int64_t npos, int64_t L, int R_,
+                                                          const double* __restrict__ st,
+                                                          const float* __restrict__ w, const float* __restrict__ bb,
+                                                          const float* __restrict__ gram, double* __restrict__ st_y) {
+    __shared__ float wb[2 * H];
+    // per (pass, wave) the segmented sums of its <= 2 groups; merged in position order into one atomic pair per
+    // group and workgroup (one pair per wave put up to ~260 waves on each group's line: atomic-bound at large L)
+    __shared__ double rs[GN_MOM_RMAX * 4 * 2][2];
+    __shared__ int64_t rgid[GN_MOM_RMAX * 4 * 2];
+    for (int i = threadIdx.x; i < 2 * H; i += 256) wb[i] = i < H ? w[i] : bb[i - H];
+    __syncthreads();
+    const int wv = threadIdx.x >> 6;
+    const int R = MULTI ? R_ : 1;     // (MULTI = false: one pass, no loop - the H = 24, 48 loop bodies spill SGPRs)
+#pragma unroll 1
+    for (int it = 0; it < R; ++it) {
+        const int64_t p0 = ((int64_t)blockIdx.x * R + it) * 256;
+        const int64_t p = p0 + threadIdx.x;
+        const bool act = p < npos;
+        const int64_t pp = act ? p : npos - 1;
+        const int64_t g = pp / L;
+        float mean, rstd;
+        gn_params(st, g, L * H, mean, rstd);
+        constexpr int HF = H % 4 == 0 ? H : (H + 7) / 8 * 8;       // f32 input row stride (H = 6: 8, dconv_conv3)
+        float x[HF];
+        const float4* hr = reinterpret_cast<const float4*>(h + pp * HF);
+#pragma unroll
+        for (int q = 0; q < HF / 4; ++q) {
+            const float4 v = hr[q];
+            x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
+        }
+        constexpr int OS = H % 8 == 0 ? H : (H + 15) / 16 * 16;     // output row stride (H = 12: rows padded to 16)
+        uint32_t pk[OS / 2];
+#pragma unroll
+        for (int j = 0; j < H; j += 2) {
+            pk[j / 2] = pack2bf(gelu_fast((x[j] - mean) * rstd * wb[j] + wb[H + j]),
+                                gelu_fast((x[j + 1] - mean) * rstd * wb[j + 1] + wb[H + j + 1]));
+            x[j] = __uint_as_float(pk[j / 2] << 16);                 // the bf16 values the 1x1 GEMM multiplies
+            x[j + 1] = __uint_as_float(pk[j / 2] & 0xFFFF0000u);
+        }
+#pragma unroll
+        for (int j = H / 2; j < OS / 2; ++j) pk[j] = 0u;
+        if (act) {
+            uint4* o = reinterpret_cast<uint4*>(out + pp * OS);
+#pragma unroll
+            for (int q = 0; q < OS / 8; ++q) o[q] = make_uint4(pk[4 * q], pk[4 * q + 1], pk[4 * q + 2], pk[4 * q + 3]);
+        }
+        // the moments are wave-uniform: scalar loads, one G row per step (the pointer is made opaque per row, so the
+        // compiler cannot hoist all H*H loads to the front, which needed ~2300 registers and spilled)
+        typedef __attribute__((address_space(4))) const float cfloat;    // constant address space: scalar loads
+        float qf = 0.f, lv = 0.f, lw = 0.f;
+#pragma unroll
+        for (int j = 0; j < H; ++j) {
+            cfloat* gr = (cfloat*)(gram + j * H);
+            asm volatile("" : "+s"(gr), "+v"(qf));              // row j's loads after row j-1's products
+            float t4[4] = {0.f, 0.f, 0.f, 0.f};                 // 4 independent chains (the FMA latency, not issue)
+#pragma unroll
+            for (int k0 = 0; k0 < H; k0 += 24) {               // (at most 24 row values in SGPRs at a time)
+                cfloat* gk = gr + k0;
+                if (k0 > 0) asm volatile("" : "+s"(gk), "+v"(t4[0]));
+#pragma unroll
+                for (int k = 0; k < (H - k0 < 24 ? H - k0 : 24); ++k) t4[k & 3] = fmaf(gk[k], x[k0 + k], t4[k & 3]);
+            }
+            qf = fmaf(x[j], (t4[0] + t4[1]) + (t4[2] + t4[3]), qf);
+            lv = fmaf(gr[H * (H - j) + j], x[j], lv);            // gram[H*H + j]      = (W^T b)_j
+            lw = fmaf(gr[H * (H - j) + H + j], x[j], lw);        // gram[H*H + H + j]  = (W^T 1)_j
+        }
+        cfloat* gt = (cfloat*)(gram + H * H + 2 * H);
+        const float sb = gt[0], sb2 = gt[1];
+        const double s1 = act ? (double)(sb + lw) : 0.0;
+        const double s2 = act ? (double)(sb2 + (2.f * lv + qf)) : 0.0;
+        // segmented wave sums: group gA of the first lane, gB of the last active lane (gA <= g <= gB, gB <= gA + 1)
+        const int64_t gA = __builtin_amdgcn_readfirstlane((int)g);
+        const int64_t last = p0 + wv * 64 + 63;
+        const int64_t gB = (last < npos ? last : npos - 1) / L;
+        const bool inA = g == gA;
+        const double a1 = wave_sum_d(inA ? s1 : 0.0), a2 = wave_sum_d(inA ? s2 : 0.0);
+        double b1 = 0.0, b2 = 0.0;
+        if (gB != gA) {
+            b1 = wave_sum_d(inA ? 0.0 : s1);
+            b2 = wave_sum_d(inA ? 0.0 : s2);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            const int e = (it * 4 + wv) * 2;
+            rgid[e] = gA; rs[e][0] = a1; rs[e][1] = a2;
+            rgid[e + 1] = gB != gA ? gB : -1; rs[e + 1][0] = b1; rs[e + 1][1] = b2;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {          // entries in position order: groups non-decreasing
+        int64_t cg = -1;
+        double c1 = 0.0, c2 = 0.0;
+        for (int e = 0; e < R * 8; ++e) {
+            const int64_t ge = rgid[e];
+            if (ge < 0) continue;
+            if (ge != cg) {
+                if (cg >= 0) {
+                    atomicAdd(&st_y[2 * cg], c1);
+                    atomicAdd(&st_y[2 * cg + 1], c2);
+                }
+                cg = ge;
+                c1 = c2 = 0.0;
+            }
+            c1 += rs[e][0];
+            c2 += rs[e][1];
+        }
+        if (cg >= 0) {
+            atomicAdd(&st_y[2 * cg], c1);
+            atomicAdd(&st_y[2 * cg + 1], c2);
+        }
+    }
+}
+
+// H = 48 with the quadratic form split over the workgroup's 4 waves: a workgroup takes 64 positions, wave w
+// writes GELU(GN(h)) of channels [w H/4, (w + 1) H/4) of all 64 (one lane per position) and its bf16-rounded values
+// into an LDS row per position, then takes G rows [w H/4, (w + 1) H/4) (scalar loads, as above) against the whole row;
+// wave 0 adds the 4 partial forms.  4x the waves of gn_gelu_mom_kernel and a quarter of its serial G-row chain per
+// wave: level 3 has only 66 k / 132 k positions, so the one-wave-per-64-positions form left the CUs idle (fenc3
+// 0.104 -> 0.075 ms, tenc3 0.103 -> 0.051 for two launches; at H = 24 the split measured slower and is not used).
+template <int H>
+__global__ __launch_bounds__(256) void gn_gelu_mom_split_kernel(const float* __restrict__ h, bf16_t* __restrict__ out,
+                                                                int64_t npos, int64_t L,
+                                                                const double* __restrict__ st,
+                                                                const float* __restrict__ w,
+                                                                const float* __restrict__ bb,
+                                                                const float* __restrict__ gram,
+                                                                double* __restrict__ st_y) {
+    constexpr int QJ = H / 4;
+    static_assert(QJ % 2 == 0, "channel pairs");
+    __shared__ float wb[2 * H];
+    __shared__ float xs[64][H + 1];          // (odd pitch: the row reads of 64 lanes hit distinct banks)
+    __shared__ float red[4][64][3];
+    for (int i = threadIdx.x; i < 2 * H; i += 256) wb[i] = i < H ? w[i] : bb[i - H];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t p = (int64_t)blockIdx.x * 64 + lane;
+    const bool act = p < npos;
+    const int64_t pp = act ? p : npos - 1;
+    const int64_t g = pp / L;
+    float mean, rstd;
+    gn_params(st, g, L * H, mean, rstd);
+    {
+        const int c0 = QJ * wv;
+        const float2* hr = reinterpret_cast<const float2*>(h + pp * H + c0);
+        uint32_t* o = reinterpret_cast<uint32_t*>(out + pp * H + c0);
+#pragma unroll
+        for (int q = 0; q < QJ / 2; ++q) {
+            const float2 v = hr[q];
+            const int c = c0 + 2 * q;
+            const uint32_t pk = pack2bf(gelu_fast((v.x - mean) * rstd * wb[c] + wb[H + c]),
+                                        gelu_fast((v.y - mean) * rstd * wb[c + 1] + wb[H + c + 1]));
+            if (act) o[q] = pk;
+            xs[lane][c] = __uint_as_float(pk << 16);
+            xs[lane][c + 1] = __uint_as_float(pk & 0xFFFF0000u);
+        }
+    }
+    __syncthreads();
+    float x[H];
+#pragma unroll
+    for (int k = 0; k < H; ++k) x[k] = xs[lane][k];
+    typedef __attribute__((address_space(4))) const float cfloat;    // constant address space: scalar loads
+    float qf = 0.f, lv = 0.f, lw = 0.f;
+    const int j0 = __builtin_amdgcn_readfirstlane(QJ * wv);
+#pragma unroll
+    for (int jj = 0; jj < QJ; ++jj) {
+        const int j = j0 + jj;
+        cfloat* gr = (cfloat*)(gram + j * H);
+        asm volatile("" : "+s"(gr), "+v"(qf));              // row j's loads after row j-1's products
+        float t4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k0 = 0; k0 < H; k0 += 24) {
+            cfloat* gk = gr + k0;
+            if (k0 > 0) asm volatile("" : "+s"(gk), "+v"(t4[0]));
+#pragma unroll
+            for (int k = 0; k < (H - k0 < 24 ? H - k0 : 24); ++k) t4[k & 3] = fmaf(gk[k], x[k0 + k], t4[k & 3]);
+        }
+        const float xj = xs[lane][j];
+        qf = fmaf(xj, (t4[0] + t4[1]) + (t4[2] + t4[3]), qf);
+        lv = fmaf(gr[H * (H - j) + j], xj, lv);             // gram[H*H + j]      = (W^T b)_j
+        lw = fmaf(gr[H * (H - j) + H + j], xj, lw);         // gram[H*H + H + j]  = (W^T 1)_j
+    }
+    red[wv][lane][0] = qf;
+    red[wv][lane][1] = lv;
+    red[wv][lane][2] = lw;
+    __syncthreads();
+    if (wv != 0) return;
+    qf = (red[0][lane][0] + red[1][lane][0]) + (red[2][lane][0] + red[3][lane][0]);
+    lv = (red[0][lane][1] + red[1][lane][1]) + (red[2][lane][1] + red[3][lane][1]);
+    lw = (red[0][lane][2] + red[1][lane][2]) + (red[2][lane][2] + red[3][lane][2]);
+    cfloat* gt = (cfloat*)(gram + H * H + 2 * H);
+    const float sb = gt[0], sb2 = gt[1];
+    const double s1 = act ? (double)(sb + lw) : 0.0;
+    const double s2 = act ? (double)(sb2 + (2.f * lv + qf)) : 0.0;
+    const int64_t gA = __builtin_amdgcn_readfirstlane((int)g);
+    const int64_t last = (int64_t)blockIdx.x * 64 + 63;
+    const int64_t gB = (last < npos ? last : npos - 1) / L;
+    const bool inA = g == gA;
+    const double a1 = wave_sum_d(inA ? s1 : 0.0), a2 = wave_sum_d(inA ? s2 : 0.0);
+    if (lane == 0) {
+        atomicAdd(&st_y[2 * gA], a1);
+        atomicAdd(&st_y[2 * gA + 1], a2);
+    }
+    if (gB != gA) {
+        const double b1 = wave_sum_d(inA ? 0.0 : s1), b2 = wave_sum_d(inA ? 0.0 : s2);
+        if (lane == 0) {
+            atomicAdd(&st_y[2 * gB], b1);
+            atomicAdd(&st_y[2 * gB + 1], b2);
+        }
+    }
+}
+
+// ---- launchers.  Each refuses with -1, before any launch, exactly where its predicate does not hold.
+static bool dconv_rows_ok(int64_t M) { return M > 0 && M < (1LL << 31); }     // (32-bit row arithmetic in the kernels)
+
+bool gn_gelu_mom_supported(int H, int64_t L) { return L >= 64 && (H == 6 || H == 12 || H == 24 || H == 48); }
+
+int gn_gelu_mom_launch(const DconvDesc& d, hipStream_t s) {
+    const int H = d.C / 8;
+    if (!gn_gelu_mom_supported(H, d.L) || d.C != 8 * H) return -1;
+    const int64_t npos = d.M, L = d.L;
+    // 256-position passes per workgroup: as many as keep >= 2048 workgroups (8 per CU), at most GN_MOM_RMAX
+    const int64_t passes = (npos + 255) / 256;
+    const int R = H <= 12 ? (int)std::max<int64_t>(1, std::min<int64_t>(GN_MOM_RMAX, passes / 2048)) : 1;
+    const dim3 grid((unsigned)((passes + R - 1) / R));
+    KScope ks(s);
+    if (ks.on())
+        ks.begin(klabel(H <= 24 ? "gn_gelu_mom_kernel<%d>" : "gn_gelu_mom_split_kernel<%d>", H), 2.0 * npos * (H * H + 2 * H),
+                 (double)npos * H * (4 + 2));
+    if (H == 6) hipLaunchKernelGGL((gn_gelu_mom_kernel<6, true>), grid, dim3(256), 0, s, d.h, d.hb, npos, L, R, d.st_h, d.g1w, d.g1b, d.gram, d.st_y);
+    else if (H == 12) hipLaunchKernelGGL((gn_gelu_mom_kernel<12, true>), grid, dim3(256), 0, s, d.h, d.hb, npos, L, R, d.st_h, d.g1w, d.g1b, d.gram, d.st_y);
+    else if (H == 24) hipLaunchKernelGGL((gn_gelu_mom_kernel<24, false>), grid, dim3(256), 0, s, d.h, d.hb, npos, L, R, d.st_h, d.g1w, d.g1b, d.gram, d.st_y);
+    else hipLaunchKernelGGL((gn_gelu_mom_split_kernel<48>), dim3((unsigned)((npos + 63) / 64)), dim3(256), 0, s, d.h, d.hb, npos, L, d.st_h, d.g1w, d.g1b, d.gram, d.st_y);
+    return (int)hipGetLastError();
+}
+
+// Grid of a weights-resident pass: 16-row units dealt to `waves`-wave workgroups, at most per_cu per CU (LDS)
+template <typename Args>
+struct DcGrid { int C, per_cu, waves; void (*kernel)(const Args); };
+template <typename Args, size_t N>
+static int dc_launch(const DcGrid<Args> (&table)[N], int C, const Args& a, hipStream_t s) {
+    for (const DcGrid<Args>& g : table) {
+        if (g.C != C) continue;
+        const int64_t units = (a.M + 15) / 16;
+        const int64_t blocks = std::min<int64_t>((int64_t)g.per_cu * device_cus(), (units + g.waves - 1) / g.waves);
+        hipLaunchKernelGGL(g.kernel, dim3((unsigned)blocks), dim3(64 * g.waves), 0, s, a);
+        return (int)hipGetLastError();
+    }
+    return -1;
+}
+// conv3 weights in LDS: 6, 10, 36 KB; 110 KB (one 16-wave workgroup per CU)
+static const DcGrid<DcConv3> kConv3Grid[] = {{48, 3, 8, dconv_conv3_kernel<48, 8>}, {96, 3, 8, dconv_conv3_kernel<96, 8>},
+                                             {192, 2, 8, dconv_conv3_kernel<192, 8>}, {384, 1, 16, dconv_conv3_kernel<384, 16>}};
+// 1x1 weights in LDS: 12, 27 (hidden rows padded to 16 channels by gn_gelu_mom), 48, 96 KB; with the rewrite 25, 77 KB
+static const DcGrid<DcApply> kApplyGrid[] = {{48, 3, 8, dconv_apply_kernel<48, 8>}, {96, 3, 8, dconv_apply_kernel<96, 8>},
+                                             {192, 2, 8, dconv_apply_kernel<192, 8>}, {384, 1, 16, dconv_apply_kernel<384, 16>}};
+static const DcGrid<DcApply> kApplyRewriteGrid[] = {{48, 3, 8, dconv_apply_kernel<48, 8, true>},
+                                                    {96, 2, 8, dconv_apply_kernel<96, 8, true>}};
+
 bool dconv_conv3_supported(int C, int H, int kp, int64_t L) {
     return (C == 48 || C == 96 || C == 192 || C == 384) && H == C / 8 && kp >= 3 * C && L >= 16;
 }
 
-int dconv_conv3_launch(const uint16_t* x, const uint16_t* w, int kp, const float* bias, float* h, double* st,
-                       int64_t M, int64_t L, int C, int dil, hipStream_t s) {
-    if (!dconv_conv3_supported(C, C / 8, kp, L) || M <= 0 || M >= (1LL << 31)) return -1;
-    DcConv3 d;
-    d.x = x; d.w = w; d.bias = bias; d.h = h; d.st = st; d.M = M; d.L = L; d.kp = kp; d.dil = dil;
-    const int cus = device_cus();
+int dconv_conv3_launch(const DconvDesc& d, hipStream_t s) {
+    const int C = d.C;
+    if (!dconv_conv3_supported(C, C / 8, d.w3_kp, d.L) || !dconv_rows_ok(d.M)) return -1;
+    const DcConv3 a = {(const uint16_t*)d.x, d.w3, d.b3, d.h, d.st_h, d.M, d.L, d.w3_kp, d.dil};
     KScope ks(s);
     if (ks.on()) {
         const double H = C / 8;
-        ks.begin(klabel("dconv_conv3_kernel<%d>", C), 2.0 * M * H * 3 * C, (double)M * (C * 2 + H * 4));
+        ks.begin(klabel("dconv_conv3_kernel<%d>", C), 2.0 * a.M * H * 3 * C, (double)a.M * (C * 2 + H * 4));
     }
-    const int64_t units = (M + 15) / 16;
-    if (C == 48) {       // 6 KB of weights
-        const int64_t blocks = std::min<int64_t>(3LL * cus, (units + 7) / 8);
-        hipLaunchKernelGGL((dconv_conv3_kernel<48, 8>), dim3((unsigned)blocks), dim3(512), 0, s, d);
-    } else if (C == 96) {       // 10 KB of weights
-        const int64_t blocks = std::min<int64_t>(3LL * cus, (units + 7) / 8);
-        hipLaunchKernelGGL((dconv_conv3_kernel<96, 8>), dim3((unsigned)blocks), dim3(512), 0, s, d);
-    } else if (C == 192) {      // 36 KB of weights: 2 eight-wave workgroups per CU
-        const int64_t blocks = std::min<int64_t>(2LL * cus, (units + 7) / 8);
-        hipLaunchKernelGGL((dconv_conv3_kernel<192, 8>), dim3((unsigned)blocks), dim3(512), 0, s, d);
-    } else {             // 110 KB: one 16-wave workgroup per CU
-        const int64_t blocks = std::min<int64_t>((int64_t)cus, (units + 15) / 16);
-        hipLaunchKernelGGL((dconv_conv3_kernel<384, 16>), dim3((unsigned)blocks), dim3(1024), 0, s, d);
-    }
-    return (int)hipGetLastError();
+    return dc_launch(kConv3Grid, C, a, s);
 }
 
 bool dconv_apply_supported(int C, int H, int kp, int64_t M) {
     return (C == 48 || C == 96 || C == 192 || C == 384) && H == C / 8 && kp == 64 && M > 0;
 }
 
-int dconv_apply_launch(const uint16_t* hb, const uint16_t* w, int kp, const float* bias, const double* st,
-                       const float* gn_w, const float* gn_b, const float* scale, uint16_t* x, int64_t M, int64_t L,
-                       int C, hipStream_t s, const DcRewrite* rwd) {
-    if (!dconv_apply_supported(C, C / 8, kp, M)) return -1;
-    if (rwd && !(C == 48 || C == 96)) return -1;
-    DcApply d;
-    d.hb = hb; d.w = w; d.bias = bias; d.st = st; d.gn_w = gn_w; d.gn_b = gn_b; d.scale = scale; d.x = x;
-    d.M = M; d.L = L; d.gn_count = L * 2 * C; d.kp = kp;
-    if (rwd) {
-        if (rwd->kp < (C + 31) / 32 * 32) return -1;
-        d.rw = rwd->w; d.rkp = rwd->kp; d.rbias = rwd->bias; d.out = rwd->out; d.c4 = rwd->c4;
-    }
-    const int cus = device_cus();
+int dconv_apply_launch(const DconvDesc& d, hipStream_t s, const DcRewrite* rwd) {
+    const int C = d.C;
+    const int64_t M = d.M;
+    if (!dconv_apply_supported(C, C / 8, d.w1_kp, M)) return -1;
+    if (rwd && (!dconv_narrow(C) || rwd->kp < (C + 31) / 32 * 32)) return -1;
+    DcApply a;
+    a.hb = d.hb; a.w = d.w1; a.bias = d.b1; a.st = d.st_y; a.gn_w = d.g2w; a.gn_b = d.g2b; a.scale = d.scale;
+    a.x = (uint16_t*)d.x; a.M = M; a.L = d.L; a.gn_count = d.L * 2 * C; a.kp = d.w1_kp;
+    if (rwd) { a.rw = rwd->w; a.rkp = rwd->kp; a.rbias = rwd->bias; a.out = rwd->out; a.c4 = rwd->c4; }
     KScope ks(s);
     if (ks.on()) {
         const double H = C / 8;
@@ -728,25 +678,27 @@ int dconv_apply_launch(const uint16_t* hb, const uint16_t* w, int kp, const floa
         else
             ks.begin(klabel("dconv_apply_kernel<%d>", C), 2.0 * M * 2 * C * H, (double)M * (H * 2 + 2.0 * C * 2));
     }
-    const int64_t units = (M + 15) / 16;
-    if (rwd) {           // C = 48: 25 KB of LDS, C = 96: 77 KB
-        const int64_t blocks = std::min<int64_t>((C == 48 ? 3LL : 2LL) * cus, (units + 7) / 8);
-        if (C == 48) hipLaunchKernelGGL((dconv_apply_kernel<48, 8, true>), dim3((unsigned)blocks), dim3(512), 0, s, d);
-        else hipLaunchKernelGGL((dconv_apply_kernel<96, 8, true>), dim3((unsigned)blocks), dim3(512), 0, s, d);
-    } else if (C == 48) {
-        const int64_t blocks = std::min<int64_t>(3LL * cus, (units + 7) / 8);
-        hipLaunchKernelGGL((dconv_apply_kernel<48, 8>), dim3((unsigned)blocks), dim3(512), 0, s, d);
-    } else if (C == 96) {       // (time-branch level 1: hidden rows padded to 16 channels by gn_gelu_mom; 27 KB of LDS)
-        const int64_t blocks = std::min<int64_t>(3LL * cus, (units + 7) / 8);
-        hipLaunchKernelGGL((dconv_apply_kernel<96, 8>), dim3((unsigned)blocks), dim3(512), 0, s, d);
-    } else if (C == 192) {      // 48 KB of weights: two 8-wave workgroups per CU
-        const int64_t blocks = std::min<int64_t>(2LL * cus, (units + 7) / 8);
-        hipLaunchKernelGGL((dconv_apply_kernel<192, 8>), dim3((unsigned)blocks), dim3(512), 0, s, d);
-    } else {             // 96 KB: one 16-wave workgroup per CU
-        const int64_t blocks = std::min<int64_t>((int64_t)cus, (units + 15) / 16);
-        hipLaunchKernelGGL((dconv_apply_kernel<384, 16>), dim3((unsigned)blocks), dim3(1024), 0, s, d);
-    }
-    return (int)hipGetLastError();
+    return rwd ? dc_launch(kApplyRewriteGrid, C, a, s) : dc_launch(kApplyGrid, C, a, s);
+}
+
+// the plan (kernels.h), by the predicates above at the packed row lengths gemm_kp (ctx.h up_gemm)
+DconvPlan dconv_plan(int mode, int C, int64_t nb, int64_t L, bool rewrite_fusable) {
+    DconvPlan p = {};
+    const int H = C / 8;
+    if ((mode != 0 && mode != 1) || !dconv_rows_ok(nb) || !dconv_rows_ok(L)) return p;
+    const int64_t M = nb * L;       // (no overflow: both factors below 2^31)
+    // (the same channel counts and packed 1x1 in every form of the layer: the apply pass's rule)
+    if (!dconv_rows_ok(M) || !dconv_apply_supported(C, H, gemm_kp(H), M)) return p;
+    p.ok = true;
+    const bool bf = dconv_bf16(mode);
+    const bool conv3 = bf && dconv_conv3_supported(C, H, gemm_kp(3 * C), L), mom = bf && gn_gelu_mom_supported(H, L);
+    p.valu = dconv_narrow(C) && !(conv3 && mom);
+    if (p.valu) return p;
+    p.conv3_mfma = conv3;
+    p.norm = mom ? DconvPlan::MOM : bf ? DconvPlan::BF16 : DconvPlan::F32;
+    p.apply_mfma = bf;
+    p.rewrite = rewrite_fusable && bf && dconv_narrow(C);
+    return p;
 }
 
 }  // namespace athd

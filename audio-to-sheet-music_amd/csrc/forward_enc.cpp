@@ -5,92 +5,65 @@
 namespace athd_fwd {
 namespace {
 
-// One encoder level's DConv (2 residual layers) on x viewed as [nb][L][C] (freq: nb = B*F rows along time).
-// Per layer: h = conv3(x) (+stats) -> GN+GELU in place -> 1x1 conv twice: pass 1 only accumulates the GroupNorm
-// statistics of its 2C outputs, pass 2 recomputes them (K = C/8 is tiny) and applies GN -> GLU -> LayerScale
-// -> residual in the epilogue, writing x in place.  The 2C-channel intermediate never touches HBM.
-// rw: the layer's rewrite fused into the second DConv layer's apply pass (bf16 mode, C = 48, 96): returns true when it
-// ran there (x then holds the first layer's output only), false when the caller must run the rewrite
+// One encoder level's DConv (2 residual layers) on x viewed as [nb][L][C] (freq: nb = B*F rows along time), launched
+// as dconv_plan (kernels.h) decides beforehand: the VALU layer, or conv3 (+stats) -> GN+GELU -> the 1x1 twice (its 2C
+// outputs never touch HBM): for their GroupNorm statistics, unless the GN+GELU pass took those from the 1x1's moments,
+// and again with GN -> GLU -> LayerScale -> residual in place.  A planned launcher that fails is an error.
+// rw: the level's rewrite; returns whether the second layer's apply pass ran it (x then holds the first layer's output)
 bool dconv(Run& r, const EncW& e, void* x, int64_t nb, int64_t L, float* hbuf, uint16_t* hbuf_b,
            const DcRewrite* rw = nullptr) {
-    bool fused = false;
-    const int ab = r.actbf ? 1 : 0;
-    const int C = e.cout, Hh = C / 8;
+    const int ab = r.actbf ? 1 : 0, C = e.cout, Hh = C / 8;
+    const DConvW& w = e.dc;
+    const DconvPlan p = dconv_plan(r.mode, C, nb, L, rw != nullptr);
+    if (!p.ok) { r.check(ATHD_EHIP, "dconv: no route"); return false; }
     for (int dd = 0; dd < 2; ++dd) {
-        const int dil = 1 << dd;
-        double *st_h = r.stats(nb), *st_y = r.stats(nb);
-        // C = 96 in the bf16 mode (the time branch's level 1; the freq level 1 is fused in fenc_row): the MFMA passes
-        // of the wide levels below (conv3, GN+GELU with the 1x1's moments, apply), the hidden rows padded to 16
-        const bool wide96 = (C == 48 || C == 96) && r.actbf && hbuf_b && e.dc.gram1b[dd] && e.dc.c3[dd].w && L >= 64;
-        if (C <= 96 && !wide96) {   // narrow levels: HBM-bound VALU kernels (dconv.hip)
+        DconvDesc d;
+        d.x = x; d.x_bf16 = ab; d.h = hbuf; d.hb = hbuf_b; d.M = nb * L; d.L = L; d.C = C; d.dil = 1 << dd;
+        d.st_h = r.stats(nb); d.st_y = r.stats(nb);
+        d.b3 = w.c3[dd].bias; d.g1w = w.g1w[dd]; d.g1b = w.g1b[dd]; d.scale = w.scale[dd];
+        if (p.valu) {   // narrow levels: HBM-bound VALU kernels (dconv_small.hip) on the natural-order f32 weights
+            d.w3f = w.w3f[dd]; d.w1f = w.w1f[dd]; d.b1 = w.b1f[dd]; d.g2w = w.g2wf[dd]; d.g2b = w.g2bf[dd];
+            d.gram = w.gram1[dd]; d.fast = r.actbf;
             KSite site(dd == 0 ? "dconv0" : "dconv1");
-            r.check(dconv_small_launch(x, ab, hbuf, nb, L, C, dil, e.dc.w3f[dd], e.dc.c3[dd].bias, e.dc.g1w[dd],
-                                       e.dc.g1b[dd], e.dc.w1f[dd], e.dc.b1f[dd], e.dc.gram1[dd], e.dc.g2wf[dd], e.dc.g2bf[dd],
-                                       e.dc.scale[dd], st_h, st_y, r.s, r.actbf), "dconv_small");
+            r.check(dconv_small_launch(d, r.s), "dconv_small");
             continue;
         }
-        GemmDesc g = conv_h(e.dc.c3[dd], x, ab, nb, L, 1, C, 3, 1, -dil, dil, L);
-        out_to(g, hbuf, 0, Hh, L);
-        g.stats = st_h;
-        int rc3 = -1;
-        if (r.actbf) {       // bf16 mode: the weights-resident conv3 pass (dconv.hip), else the tiled GEMM
+        d.w3 = (const uint16_t*)w.c3[dd].w; d.w3_kp = w.c3[dd].Kp; d.w1 = (const uint16_t*)w.c1[dd].w; d.w1_kp = w.c1[dd].Kp;
+        d.b1 = w.c1[dd].bias; d.g2w = w.g2w[dd]; d.g2b = w.g2b[dd]; d.gram = w.gram1b[dd];
+        if (p.conv3_mfma) {
             KSite site("dconv.conv3");
-            rc3 = dconv_conv3_launch((const uint16_t*)x, (const uint16_t*)e.dc.c3[dd].w, e.dc.c3[dd].Kp,
-                                     e.dc.c3[dd].bias, hbuf, st_h, nb * L, L, C, dil, r.s);
+            r.check(dconv_conv3_launch(d, r.s), "dconv_conv3");
+        } else {
+            GemmDesc g = conv_h(w.c3[dd], x, ab, nb, L, 1, C, 3, 1, -d.dil, d.dil, L);
+            out_to(g, hbuf, 0, Hh, L);
+            g.stats = d.st_h;
+            r.gemm(g, "dconv.conv3");
         }
-        if (rc3 > 0 || (rc3 != 0 && wide96)) {   // (wide96: the padded hidden rows exist in the MFMA pass only)
-            r.check(rc3 > 0 ? rc3 : ATHD_EHIP, "dconv_conv3");
-            return fused;
-        }
-        if (rc3 != 0) r.gemm(g, "dconv.conv3");
-        // bf16 mode: GELU(GN(h)) written once as bf16, so both 1x1 passes read half the bytes and run on the bf16
-        // MFMA GEMMs (gemm3 / gemm5) instead of converting fp32 A on load
-        const bool hb = r.actbf && hbuf_b && (Hh % 8 == 0 || wide96);
-        // the 1x1's GroupNorm statistics from its moments, taken by the GN+GELU pass (no statistics GEMM pass)
-        bool mom = false;
+        // bf16 mode: GELU(GN(h)) written once as bf16 (hbuf_b), so both 1x1 passes read half the bytes
+        const bool hb = p.norm != DconvPlan::F32;
         {
             KSite site("dconv.gn_gelu");
-            if (hb && e.dc.gram1b[dd])
-                mom = gn_gelu_mom_launch(hbuf, hbuf_b, (int)nb, L, Hh, st_h, e.dc.g1w[dd], e.dc.g1b[dd], e.dc.gram1b[dd],
-                                         st_y, r.s) == 0;
-            if (!mom && wide96) {
-                // the padded-row layout of the narrow MFMA passes (hidden rows of 16) has no other GN+GELU pass
-                r.check(ATHD_EHIP, "dconv gn_gelu_mom (C = 48 / 96)");
-                return false;
-            }
-            if (mom) {}      // (statistics of the 1x1 already in st_y)
-            else if (hb) gn_gelu_bf16_launch(hbuf, hbuf_b, (int)nb, L * Hh, Hh, st_h, e.dc.g1w[dd], e.dc.g1b[dd], r.s);
-            else gn_gelu_launch(hbuf, (int)nb, L * Hh, Hh, st_h, e.dc.g1w[dd], e.dc.g1b[dd], r.s, r.actbf);
+            if (p.norm == DconvPlan::MOM) r.check(gn_gelu_mom_launch(d, r.s), "gn_gelu_mom");
+            else if (hb) gn_gelu_bf16_launch(hbuf, hbuf_b, (int)nb, L * Hh, Hh, d.st_h, d.g1w, d.g1b, r.s);
+            else gn_gelu_launch(hbuf, (int)nb, L * Hh, Hh, d.st_h, d.g1w, d.g1b, r.s, r.actbf);
         }
-        GemmDesc g2 = conv1(e.dc.c1[dd], hb ? (const void*)hbuf_b : (const void*)hbuf, hb ? 1 : 0, nb, L, 1, Hh);
+        GemmDesc g2 = conv1(w.c1[dd], hb ? (const void*)hbuf_b : (const void*)hbuf, hb ? 1 : 0, nb, L, 1, Hh);
         out_to(g2, x, ab, C, L);
-        if (!mom) {
+        if (p.norm != DconvPlan::MOM) {
             GemmDesc g1 = g2;
-            g1.stats = st_y; g1.store = 0;
+            g1.stats = d.st_y; g1.store = 0;
             r.gemm(g1, "dconv.conv1x1.stats");
         }
-        g2.act = ACT_GLU; g2.gn_stats = st_y; g2.gn_count = L * 2 * C; g2.gn_w = e.dc.g2w[dd]; g2.gn_b = e.dc.g2b[dd];
-        g2.res = x; g2.res_bf16 = ab; g2.res_scale = e.dc.scale[dd];
-        // bf16 mode: the weights-resident apply pass (dconv.hip dconv_apply_kernel), else the GEMM with its epilogue
-        int rc = -1;
-        if (hb) {
+        if (p.apply_mfma) {
             KSite site("dconv.conv1x1.apply");
-            const DcRewrite* rwd = dd == 1 && wide96 ? rw : nullptr;
-            // rc -1: rejected before any launch (fall back); rc > 0: a HIP error after the in-place kernel was issued,
-            // so x may already hold the residual update: report it, never run a second apply over it
-            auto apply = [&](const DcRewrite* rwa) {
-                return dconv_apply_launch(hbuf_b, (const uint16_t*)e.dc.c1[dd].w, e.dc.c1[dd].Kp, e.dc.c1[dd].bias, st_y,
-                                          e.dc.g2w[dd], e.dc.g2b[dd], e.dc.scale[dd], (uint16_t*)x, nb * L, L, C, r.s, rwa);
-            };
-            rc = apply(rwd);
-            if (rc == 0 && rwd) fused = true;
-            if (rc == -1 && rwd) rc = apply(nullptr);     // (without the rewrite, then the caller's GEMM)
-            if (rc > 0) { r.check(rc, "dconv_apply"); return fused; }
-            if (rc == -1 && wide96) { r.check(ATHD_EHIP, "dconv_apply (C = 48 / 96, padded hidden rows)"); return fused; }
+            r.check(dconv_apply_launch(d, r.s, dd == 1 && p.rewrite ? rw : nullptr), "dconv_apply");
+        } else {
+            g2.act = ACT_GLU; g2.gn_stats = d.st_y; g2.gn_count = L * 2 * C; g2.gn_w = d.g2w; g2.gn_b = d.g2b;
+            g2.res = x; g2.res_bf16 = ab; g2.res_scale = d.scale;
+            r.gemm(g2, "dconv.conv1x1.apply");
         }
-        if (rc != 0) r.gemm(g2, "dconv.conv1x1.apply");
     }
-    return fused;
+    return p.rewrite;
 }
 
 // the rewrite 1x1 + GLU of an encoder level: y [nb][H][W][C] -> saved, its first 4 channels also to c4 (level 0)
@@ -112,8 +85,8 @@ void fenc_level(Run& r, const Dims& d, const Bufs& b, int i) {
     const int C = e.cout, Fi = d.F[i], Fo = d.F[i + 1];
     const int eab = r.actbf ? 1 : 0;       // encoder activations in bf16 (throughput mode)
     const void* in = i == 0 ? (const void*)b.specT : (const void*)b.saved[i - 1];
-    // the fused narrow level (fenc_row.hip) applies: bf16 mode, C in {48, 96}, T <= 272, padded conv3 packed
-    if (r.actbf && r.sw.fenc_row && e.dc.c3p[0].w && e.dc.c3p[1].w && fenc_row_supported(e.cin, e.cout, (int)Ts)) {
+    // the fused narrow level (fenc_row.hip) applies: bf16 mode, C in {48, 96}, T <= 272
+    if (r.actbf && r.sw.fenc_row && fenc_row_supported(e.cin, e.cout, (int)Ts)) {
         // conv + GELU + DConv + rewrite GLU in one kernel per (b, f) row
         FencRowDesc fr;
         fr.in = in; fr.a_norm = i == 0 ? b.snorm : nullptr;
@@ -168,7 +141,7 @@ void tenc_level(Run& r, const Dims& d, const Bufs& b, int i, const float* wav) {
     DcRewrite rwt;
     rwt.w = (const uint16_t*)et.rewrite_perm.w; rwt.kp = et.rewrite_perm.Kp; rwt.bias = et.rewrite_perm.bias;
     rwt.out = (uint16_t*)b.saved_t[i]; rwt.c4 = (uint16_t*)c4;
-    if (!dconv(r, et, b.ybuf_t, B, Lo, b.hbuf_t, b.hbuf_b_t, et.rewrite_perm.w ? &rwt : nullptr))
+    if (!dconv(r, et, b.ybuf_t, B, Lo, b.hbuf_t, b.hbuf_b_t, &rwt))
         r.gemm(rewrite_desc(et, b.ybuf_t, eab, B, Lo, 1, b.saved_t[i], c4), "tenc.rewrite");
 }
 

@@ -13,6 +13,9 @@ namespace athd {
 
 enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_GLU = 2 };
 
+// row length Kp that a K-wide weight row is packed to (ctx.h up_gemm)
+inline int gemm_kp(int K) { return (K + 63) / 64 * 64; }
+
 // n / d for 0 <= n < 2^31 as a multiply-high and a shift (Granlund-Montgomery with a 31+l bit reciprocal:
 // mul = ceil(2^(31+l) / d), l = ceil(log2 d), exact for every n < 2^31).  Filled by gemm_launch; the kernels' row
 // index decompositions (m -> w, h, b) and GroupNorm group indices use it instead of the ~30-instruction integer

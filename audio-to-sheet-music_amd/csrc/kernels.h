@@ -45,10 +45,6 @@ void gn_gelu_launch(float* h, int nb, int64_t per_batch, int H, const double* st
 // out[nb][per_batch] (bf16) = GELU_fast(GN(h)); per_batch % 8 == 0, H % 8 == 0
 void gn_gelu_bf16_launch(const float* h, uint16_t* out, int nb, int64_t per_batch, int H, const double* stats,
                          const float* w, const float* b, hipStream_t s);
-// gn_gelu_bf16 on [nb][L][H] (H = 24 / 48, L >= 64) plus the following 1x1 conv's GroupNorm {sum, sumsq} per nb
-// into st_y from its moments `gram` (ctx.h conv1x1_moments, bf16-rounded weights); -1 if the shape is not covered
-int gn_gelu_mom_launch(const float* h, uint16_t* out, int nb, int64_t L, int H, const double* stats, const float* w,
-                       const float* b, const float* gram, double* st_y, hipStream_t s);
 void gn_gelu_bf16in_launch(const uint16_t* h, uint16_t* out, int nb, int64_t per_batch, int H, const double* stats,
                            const float* w, const float* b, hipStream_t s);
 // x[nb][N][C] = GN(x) in place
@@ -91,6 +87,9 @@ struct MergeDesc {
     int fast_gelu = 0;                            // bf16 mode: branch-free erf
 };
 int dec_merge_launch(const MergeDesc& d, hipStream_t s);   // -1: P > 256 or NI % P != 0
+// positional tables of the cross-transformer (computed on device with the fp32 op order of demucs)
+void pos2d_launch(float* out, int Fr, int T1, int C, hipStream_t s);   // out[(f*T1+t)][C]
+void pos1d_launch(float* out, int T2, int C, hipStream_t s);           // out[t][C]
 // fdec_lr.hip: FreqDecoder level 1 from the 32-row level-0 output (re-associated ConvT; see fdec_lr.hip).
 // Z [NI][Hs][W][8*Co] = W_k S[j] per tap k; Zs [NI/P][Hk][W][8*Co] = W_k skip3[m]; skip [NI/P][H_skip][W][C_skip].
 // per output-row step v of the level-1 low-rank decoder (fdec_lr.hip): the resize lerps of the Z rows (Hs -> Hd), the
@@ -193,12 +192,43 @@ struct ConvT4Desc {
 };
 bool convt4_supported(int cin, int cout, int64_t nb, int64_t H, int64_t W);
 int convt4_launch(const ConvT4Desc& d, hipStream_t s);
-// dconv.hip: one DConv layer (conv3 -> GN -> GELU -> 1x1 -> GN -> GLU -> LayerScale -> residual) for C in {48, 96}
-// x: [nb][L][C] f32 or bf16 (x_bf16), updated in place; h: [nb][L][C/8] f32 scratch
-// dconv.hip, bf16 mode, MFMA passes (C = 48, 96, 192, 384): the DConv 1x1 apply x += scale * GLU(GN(W1 hb + b1))
-// (hb [M][HS] with HS = C/8, or 16 for C = 48, 96; x [M][C]; GroupNorm groups of L rows); -1 if the shape is not
-// covered.  With rw (C = 48, 96) the updated rows are not stored: the encoder layer's rewrite out = GLU(Wr x + br)
-// runs on them in registers (rw: [2C][kp] GLU-interleaved rows in the K order of ctx.h dconv_rewrite_perm).
+// ---- DConv: one residual layer of an encoder level, x += scale * GLU(GN(W1 GELU(GN(conv3(x))) + b1)), x [M][C] in
+// GroupNorm groups of L rows (M = nb L in the forward; the MFMA conv3 / apply passes also take a short last group).
+// What athd_finalize packs per (mode, C) (mode 0 = f32, 1 = bf16), and so what dconv_plan may route to:
+inline bool dconv_narrow(int C) { return C == 48 || C == 96; }    // the VALU layer's natural-order f32 weights + moments
+inline bool dconv_bf16(int mode) { return mode == 1; }            // the bf16-rounded 1x1 moments (gn_gelu_mom, fenc_row);
+                                                                  // narrow: conv3 rows padded to 16, permuted rewrite
+// The launches of a level's two layers, decided by the launchers' own predicates before anything runs
+struct DconvPlan {
+    bool ok;            // false: no route (C, mode, or M = nb L outside (0, 2^31))
+    bool valu;          // the whole layer in dconv_small_launch; the fields below unused
+    bool conv3_mfma;    // dconv_conv3_launch, else the tiled GEMM
+    enum Norm { MOM, BF16, F32 } norm;   // MOM: gn_gelu_mom (1x1 statistics from its moments), else + a statistics GEMM
+    bool apply_mfma;    // dconv_apply_launch, else the GEMM with the GN -> GLU -> residual epilogue
+    bool rewrite;       // second layer: the level's rewrite fused into the apply pass
+};
+DconvPlan dconv_plan(int mode, int C, int64_t nb, int64_t L, bool rewrite_fusable);
+// One layer's operands for the launchers its plan names (forward_enc.cpp dconv)
+struct DconvDesc {
+    void* x = nullptr; int x_bf16 = 0;              // [M][C], updated in place
+    float* h = nullptr;                             // conv3 output [M][C/8] f32 (MFMA passes, C = 48: rows of 8)
+    uint16_t* hb = nullptr;                         // MFMA passes: GELU(GN(h)) bf16 [M][C/8] (C = 48, 96: rows of 16)
+    double *st_h = nullptr, *st_y = nullptr;        // per group {sum, sumsq} of h / of the 1x1's 2C outputs
+    int64_t M = 0, L = 0; int C = 0, dil = 1;
+    const float *w3f = nullptr, *w1f = nullptr;     // VALU layer: f32 conv3 [C/8][tap * C + ci], 1x1 [2C][C/8]
+    bool fast = false;                              // VALU layer: the bf16 mode's branch-free GELU / sigmoid
+    const uint16_t *w3 = nullptr, *w1 = nullptr;    // MFMA passes: bf16 conv3 [16 n][w3_kp], 1x1 [2C][w1_kp] GLU-interleaved
+    int w3_kp = 0, w1_kp = 0;
+    const float *b3 = nullptr, *g1w = nullptr, *g1b = nullptr, *scale = nullptr;
+    const float *b1 = nullptr, *g2w = nullptr, *g2b = nullptr;   // in the row order of the 1x1 weights in use
+    const float* gram = nullptr;                    // ctx.h conv1x1_moments of the 1x1 weights in use
+};
+// dconv_small.hip: the layer as three VALU kernels (C = 48, 96; M = nb L); -2 if the shape is not covered
+int dconv_small_launch(const DconvDesc& d, hipStream_t s);
+// dconv.hip: the layer as three weights-resident passes (bf16 mode); -1 before any launch unless the predicate holds.
+// conv3 + GroupNorm statistics of h; hb = bf16(GELU(GN(h))) + the 1x1's statistics from d.gram (M = nb L); the 1x1
+// apply, with rw (C = 48, 96) followed in registers by the level's rewrite out = GLU(Wr x + br) instead of the store to
+// x (rw.w: [2C][kp] GLU-interleaved rows in the K order of ctx.h dconv_rewrite_perm)
 struct DcRewrite {
     const uint16_t* w;
     int kp;
@@ -206,22 +236,12 @@ struct DcRewrite {
     uint16_t* out;     // [M][C] bf16
     uint16_t* c4;      // optional [M][4]
 };
-// conv3 (C -> C/8, 3 taps at dilation dil, zero padding at each group's ends) + GroupNorm {sum, sumsq} of h per group
-// of L rows; x bf16 [M][C], h f32 [M][HF] (HF = C/8, or 8 for C = 48); -1 if the shape is not covered
-int dconv_conv3_launch(const uint16_t* x, const uint16_t* w, int kp, const float* bias, float* h, double* st,
-                       int64_t M, int64_t L, int C, int dil, hipStream_t s);
-int dconv_apply_launch(const uint16_t* hb, const uint16_t* w, int kp, const float* bias, const double* st,
-                       const float* gn_w, const float* gn_b, const float* scale, uint16_t* x, int64_t M, int64_t L,
-                       int C, hipStream_t s, const DcRewrite* rw = nullptr);
-int dconv_small_launch(void* x, int x_bf16, float* h, int64_t nb, int64_t L, int C, int dil, const float* w3,
-                       const float* b3, const float* g1w, const float* g1b, const float* w1, const float* b1,
-                       const float* gram1, const float* g2w, const float* g2b, const float* scale, double* st_h,
-                       double* st_y, hipStream_t s, bool fast);
-// (B, 2, T) -> (B, T, 2)
-void wav_interleave_launch(const float* wav, int nb, int64_t T, float* out, hipStream_t s);
-// positional tables of the cross-transformer (computed on device with the fp32 op order of demucs)
-void pos2d_launch(float* out, int Fr, int T1, int C, hipStream_t s);   // out[(f*T1+t)][C]
-void pos1d_launch(float* out, int T2, int C, hipStream_t s);           // out[t][C]
+bool dconv_conv3_supported(int C, int H, int kp, int64_t L);
+bool gn_gelu_mom_supported(int H, int64_t L);
+bool dconv_apply_supported(int C, int H, int kp, int64_t M);
+int dconv_conv3_launch(const DconvDesc& d, hipStream_t s);
+int gn_gelu_mom_launch(const DconvDesc& d, hipStream_t s);
+int dconv_apply_launch(const DconvDesc& d, hipStream_t s, const DcRewrite* rw = nullptr);
 
 // track.hip: window overlap-add of test_inference.py:92-141 (mode 0) and benchmark.py:155-204 (mode 1, weighted;
 // wsum != nullptr: unnormalised partial span + weight sums), sdr_loss / sisdr_loss (src/loss.py:9-68)

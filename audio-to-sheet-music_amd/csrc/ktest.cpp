@@ -10,10 +10,7 @@
 #include "gemm.h"
 #include "kernels.h"
 
-namespace athd {   // dconv.hip: the launchers' own shape predicates (no header declares them)
-bool dconv_conv3_supported(int C, int H, int kp, int64_t L);
-bool dconv_apply_supported(int C, int H, int kp, int64_t M);
-// norm.hip, dec_last.hip, fdec1f.hip: the tuning constants next to their launchers
+namespace athd {   // norm.hip, dec_last.hip, fdec1f.hip: the tuning constants next to their launchers
 int dec_merge_run();
 int dec_merge_maxp();
 int dec_last_const(int which);
@@ -182,28 +179,36 @@ int kt_gn_gelu_bf16(const float* h, uint16_t* out, int64_t nb, int64_t per_batch
 }
 // ---- the DConv kernels and the fused encoder rows ----
 int kt_dconv_conv3(const KtConv3* k, void* stream) {
-    return dconv_conv3_launch((const uint16_t*)k->x, (const uint16_t*)k->w, (int)k->kp, (const float*)k->bias,
-                              (float*)k->h, (double*)k->st, k->M, k->L, (int)k->C, (int)k->dil, (hipStream_t)stream);
+    DconvDesc d;
+    d.x = k->x; d.w3 = (const uint16_t*)k->w; d.w3_kp = (int)k->kp; d.b3 = (const float*)k->bias; d.h = (float*)k->h;
+    d.st_h = (double*)k->st; d.M = k->M; d.L = k->L; d.C = (int)k->C; d.dil = (int)k->dil;
+    return dconv_conv3_launch(d, (hipStream_t)stream);
 }
 int kt_dconv_apply(const KtApply* k, void* stream) {
     DcRewrite rw;
     rw.w = (const uint16_t*)k->rw_w; rw.kp = (int)k->rw_kp; rw.bias = (const float*)k->rw_bias;
     rw.out = (uint16_t*)k->rw_out; rw.c4 = (uint16_t*)k->rw_c4;
-    return dconv_apply_launch((const uint16_t*)k->hb, (const uint16_t*)k->w, (int)k->kp, (const float*)k->bias,
-                              (const double*)k->st, (const float*)k->gn_w, (const float*)k->gn_b, (const float*)k->scale,
-                              (uint16_t*)k->x, k->M, k->L, (int)k->C, (hipStream_t)stream, k->rewrite ? &rw : nullptr);
+    DconvDesc d;
+    d.hb = (uint16_t*)k->hb; d.w1 = (const uint16_t*)k->w; d.w1_kp = (int)k->kp; d.b1 = (const float*)k->bias;
+    d.st_y = (double*)k->st; d.g2w = (const float*)k->gn_w; d.g2b = (const float*)k->gn_b; d.scale = (const float*)k->scale;
+    d.x = k->x; d.M = k->M; d.L = k->L; d.C = (int)k->C;
+    return dconv_apply_launch(d, (hipStream_t)stream, k->rewrite ? &rw : nullptr);
 }
 int kt_dconv_small(const KtDcSmall* k, void* stream) {
-    return dconv_small_launch(k->x, (int)k->x_bf16, (float*)k->h, k->nb, k->L, (int)k->C, (int)k->dil,
-                              (const float*)k->w3, (const float*)k->b3, (const float*)k->g1w, (const float*)k->g1b,
-                              (const float*)k->w1, (const float*)k->b1, (const float*)k->gram1, (const float*)k->g2w,
-                              (const float*)k->g2b, (const float*)k->scale, (double*)k->st_h, (double*)k->st_y,
-                              (hipStream_t)stream, k->fast != 0);
+    DconvDesc d;
+    d.x = k->x; d.x_bf16 = (int)k->x_bf16; d.h = (float*)k->h; d.M = k->nb * k->L; d.L = k->L; d.C = (int)k->C;
+    d.dil = (int)k->dil; d.w3f = (const float*)k->w3; d.b3 = (const float*)k->b3; d.g1w = (const float*)k->g1w;
+    d.g1b = (const float*)k->g1b; d.w1f = (const float*)k->w1; d.b1 = (const float*)k->b1; d.gram = (const float*)k->gram1;
+    d.g2w = (const float*)k->g2w; d.g2b = (const float*)k->g2b; d.scale = (const float*)k->scale;
+    d.st_h = (double*)k->st_h; d.st_y = (double*)k->st_y; d.fast = k->fast != 0;
+    return dconv_small_launch(d, (hipStream_t)stream);
 }
 int kt_gn_gelu_mom(const KtGnMom* k, void* stream) {
-    return gn_gelu_mom_launch((const float*)k->h, (uint16_t*)k->out, (int)k->nb, k->L, (int)k->H, (const double*)k->stats,
-                              (const float*)k->w, (const float*)k->b, (const float*)k->gram, (double*)k->st_y,
-                              (hipStream_t)stream);
+    DconvDesc d;
+    d.h = (float*)k->h; d.hb = (uint16_t*)k->out; d.M = k->nb * k->L; d.L = k->L; d.C = 8 * (int)k->H;
+    d.st_h = (double*)k->stats; d.g1w = (const float*)k->w; d.g1b = (const float*)k->b; d.gram = (const float*)k->gram;
+    d.st_y = (double*)k->st_y;
+    return gn_gelu_mom_launch(d, (hipStream_t)stream);
 }
 int kt_gn_gelu_bf16in(const uint16_t* h, uint16_t* out, int64_t nb, int64_t per_batch, int64_t H, const double* stats,
                       const float* w, const float* b, void* stream) {
@@ -232,6 +237,12 @@ int kt_dconv_conv3_supported(int64_t C, int64_t H, int64_t kp, int64_t L) {
 }
 int kt_dconv_apply_supported(int64_t C, int64_t H, int64_t kp, int64_t M) {
     return dconv_apply_supported((int)C, (int)H, (int)kp, M);
+}
+int kt_gn_gelu_mom_supported(int64_t H, int64_t L) { return gn_gelu_mom_supported((int)H, L); }
+// out = {ok, valu, conv3_mfma, norm, apply_mfma, rewrite}
+void kt_dconv_plan(int64_t mode, int64_t C, int64_t nb, int64_t L, int64_t rewrite_fusable, int64_t* out) {
+    const DconvPlan p = dconv_plan((int)mode, (int)C, nb, L, rewrite_fusable != 0);
+    out[0] = p.ok; out[1] = p.valu; out[2] = p.conv3_mfma; out[3] = p.norm; out[4] = p.apply_mfma; out[5] = p.rewrite;
 }
 
 // ---- the host-side packers of ctx.h (no GPU) ----

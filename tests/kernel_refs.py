@@ -1133,3 +1133,20 @@ def fdec1_gram_stats_ref(Zr, amb, Zs, bias, Hd, P):
     t1 = tY.sum(axis=ax) + n * E32 * Ya.sum(axis=ax)
     t2 = (2 * np.abs(Y) * tY + tY * tY).sum(axis=ax) + n * E32 * (Ya * Ya).sum(axis=ax)
     return st, np.stack([t1, t2], -1), Y
+
+
+# ---------------------------------------------------------------------------------------------- encoder level shapes
+ENC_CH = (48, 96, 192, 384)
+
+
+def encoder_levels(T, B):
+    """The DConv problem of every encoder level for B segments of T samples (csrc/forward_plan.cpp make_dims):
+    {stage: (C, nb, L, cin, rewrite_fusable)}.  Frequency level i: nb = B F[i + 1] rows of Tspec = ceil(T / 1024) frames;
+    time level i: nb = B rows of L[i + 1] = ceil(L[i] / 4) samples, the only one whose rewrite the apply pass can take."""
+    Ts, F, L = -(-T // 1024), 2048, T
+    out = {}
+    for i, C in enumerate(ENC_CH):
+        F, L = F // 4, -(-L // 4)
+        out["fenc%d" % i] = (C, B * F, Ts, 4 if i == 0 else ENC_CH[i - 1], 0)
+        out["tenc%d" % i] = (C, B, L, 2 if i == 0 else ENC_CH[i - 1], 1)
+    return out

@@ -90,6 +90,9 @@ lib.kt_gn_gelu_bf16in.argtypes = [_P, _P, _I, _I, _I, _P, _P, _P, _P]
 lib.kt_fenc_row_supported.argtypes = [_I, _I, _I]
 lib.kt_dconv_conv3_supported.argtypes = [_I, _I, _I, _I]
 lib.kt_dconv_apply_supported.argtypes = [_I, _I, _I, _I]
+lib.kt_gn_gelu_mom_supported.argtypes = [_I, _I]
+lib.kt_dconv_plan.restype = None
+lib.kt_dconv_plan.argtypes = [_I, _I, _I, _I, _I, _P]
 for _n in ("glu_src", "rewrite_perm", "host_f2bf"):
     getattr(lib, "kt_" + _n).restype = _I
 lib.kt_glu_src.argtypes = [_I, _I]
@@ -136,6 +139,17 @@ def conv1x1_moments(w, b, round_bf16):
     out = np.zeros(H * H + 2 * H + 2, dtype=np.float32)
     lib.kt_conv1x1_moments(w.ctypes.data, b.ctypes.data, N, H, int(round_bf16), out.ctypes.data)
     return out
+
+
+PLAN_FIELDS = "ok valu conv3_mfma norm apply_mfma rewrite".split()
+NORM_MOM, NORM_BF16, NORM_F32 = 0, 1, 2
+
+
+def dconv_plan(mode, C, nb, L, rewrite_fusable):
+    """kernels.h dconv_plan (mode 0 = f32, 1 = bf16) -> {field: int}; norm is one of NORM_*"""
+    out = (ctypes.c_int64 * len(PLAN_FIELDS))()
+    lib.kt_dconv_plan(mode, C, nb, L, int(rewrite_fusable), out)
+    return dict(zip(PLAN_FIELDS, out))
 
 
 def sizes_match():

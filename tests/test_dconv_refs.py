@@ -85,6 +85,76 @@ def test_predicates(kt):
     assert L.kt_dconv_conv3_supported(48, 6, 143, 16) == 0 and L.kt_dconv_conv3_supported(48, 6, 144, 15) == 0
     assert [L.kt_dconv_apply_supported(C, C // 8, 64, 1) for C in (48, 64, 96, 192, 384)] == [1, 0, 1, 1, 1]
     assert L.kt_dconv_apply_supported(48, 6, 128, 1) == 0 and L.kt_dconv_apply_supported(48, 6, 64, 0) == 0
+    assert [L.kt_gn_gelu_mom_supported(H, 64) for H in (6, 8, 12, 24, 48)] == [1, 0, 1, 1, 1]
+    assert L.kt_gn_gelu_mom_supported(6, 63) == 0
+
+
+# ------------------------------------------------------------------------------------------------ the layer plan
+PLAN_L = (1, 15, 16, 63, 64, 65, 259, 66150)
+PLAN_T = (4096, 33297, 44100, 264600, 300000)
+
+
+def _plan_table(kt, mode, C, L, rewrite_fusable):
+    """DESIGN.md's plan table, row by row (M = nb L inside (0, 2^31))"""
+    valu = dict(ok=1, valu=1, conv3_mfma=0, norm=0, apply_mfma=0, rewrite=0)
+    if mode == 0:
+        return valu if C <= 96 else dict(ok=1, valu=0, conv3_mfma=0, norm=kt.NORM_F32, apply_mfma=0, rewrite=0)
+    if C <= 96:
+        if L < 64:
+            return valu
+        return dict(ok=1, valu=0, conv3_mfma=1, norm=kt.NORM_MOM, apply_mfma=1, rewrite=int(rewrite_fusable))
+    return dict(ok=1, valu=0, conv3_mfma=int(L >= 16), norm=kt.NORM_MOM if L >= 64 else kt.NORM_BF16, apply_mfma=1,
+                rewrite=0)
+
+
+def _planned_launchers_accept(kt, p, C, nb, L):
+    """a planned launcher cannot refuse: its own predicate holds for the weights as athd_finalize packs them"""
+    H = C // 8
+    if p["conv3_mfma"]:
+        assert kt.lib.kt_dconv_conv3_supported(C, H, (3 * C + 63) // 64 * 64, L) == 1 and 0 < nb * L < 2 ** 31
+    if p["apply_mfma"]:
+        assert kt.lib.kt_dconv_apply_supported(C, H, 64, nb * L) == 1
+    if not p["valu"] and p["norm"] == kt.NORM_MOM:
+        assert kt.lib.kt_gn_gelu_mom_supported(H, L) == 1
+    if p["rewrite"]:
+        assert p["apply_mfma"] and C in (48, 96)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("C", [48, 96, 192, 384])
+def test_dconv_plan_table(kt, mode, C):
+    for L in PLAN_L:
+        for nb in (1, 8):
+            for rw in (0, 1):
+                p = kt.dconv_plan(mode, C, nb, L, rw)
+                assert p == _plan_table(kt, mode, C, L, rw), (mode, C, nb, L, rw, p)
+                _planned_launchers_accept(kt, p, C, nb, L)
+
+
+@pytest.mark.parametrize("T", PLAN_T)
+def test_dconv_plan_model_levels(kt, T):
+    for B in (1, 2):
+        for mode in (0, 1):
+            for stage, (C, nb, L, _, rw) in kr.encoder_levels(T, B).items():
+                p = kt.dconv_plan(mode, C, nb, L, rw)
+                assert p == _plan_table(kt, mode, C, L, rw), (stage, mode, B, p)
+                _planned_launchers_accept(kt, p, C, nb, L)
+    lv = kr.encoder_levels(T, 1)
+    assert [lv["fenc%d" % i][1:3] for i in range(4)] == [(F, -(-T // 1024)) for F in (512, 128, 32, 8)]
+    Lt = T
+    for i in range(4):
+        Lt = (Lt + 3) // 4
+        assert lv["tenc%d" % i][1:3] == (1, Lt)
+
+
+def test_dconv_plan_no_route(kt):
+    """ok == 0: a channel count no kernel has, a mode outside {0, 1}, M = nb L outside (0, 2^31)"""
+    bad = [(1, 64, 1, 64), (0, 64, 1, 64), (2, 48, 1, 64), (-1, 192, 1, 64), (1, 48, 0, 64), (1, 48, 1, 0),
+           (0, 192, 0, 64), (1, 384, -1, 64), (1, 192, 2 ** 31 // 64, 64), (0, 48, 2 ** 20, 2 ** 11)]
+    for mode, C, nb, L in bad:
+        for rw in (0, 1):
+            assert kt.dconv_plan(mode, C, nb, L, rw) == dict.fromkeys(kt.PLAN_FIELDS, 0), (mode, C, nb, L)
+    assert kt.dconv_plan(1, 192, 2 ** 31 // 64 - 1, 64, 0)["ok"] == 1 and kt.dconv_plan(1, 192, 2 ** 31 - 1, 1, 0)["ok"] == 1
 
 
 # ------------------------------------------------------------------------------------------------ vs torch.nn.functional

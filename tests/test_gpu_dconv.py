@@ -1,4 +1,4 @@
-"""Kernel-level parity of the encoder's DConv kernels (csrc/dconv.hip, gn_gelu_mom / gn_gelu_bf16in of csrc/norm.hip)
+"""Kernel-level parity of the encoder's DConv kernels (csrc/dconv.hip, csrc/dconv_small.hip, gn_gelu_bf16in of csrc/norm.hip)
 and the fused encoder rows (csrc/fenc_row.hip) against the float64 references and derived tolerances of
 tests/kernel_refs.py, through libathd_ktest.so.
 
@@ -50,8 +50,8 @@ def _out16(kt, n, guard):
 
 # ===================================================================================================== dconv_conv3
 C3_SHAPES = [(1, 16), (3, 17), (5, 31), (2, 64), (3, 259)]
-# workgroups per CU and waves per workgroup of dconv_conv3_launch / dconv_apply_launch (csrc/dconv.hip: the
-# `blocks = min(k * cus, ...)` lines and the kernels' NW template arguments; the fused rewrite: `(C == 48 ? 3 : 2) * cus`).
+# workgroups per CU and waves per workgroup of dconv_conv3_launch / dconv_apply_launch (csrc/dconv.hip: the tables
+# kConv3Grid / kApplyGrid, and kApplyRewriteGrid for the fused rewrite).
 # A copy: when a launcher's grid changes, change it here too, or the two-units-per-wave cases stop reaching their path.
 DC_GRID = {48: (3, 8), 96: (3, 8), 192: (2, 8), 384: (1, 16)}
 RW_GRID = {48: (3, 8), 96: (2, 8)}

@@ -542,6 +542,70 @@ def test_encoder_levels_bf16_stage(models, oracle_model, text_table, monkeypatch
     assert not bad, (bad, res)
 
 
+def _dconv_family(kernel):
+    if kernel.startswith("gemm"):
+        return "gemm"
+    if kernel.startswith("gn_gelu_mom"):
+        return "gn_gelu_mom"
+    if kernel.startswith("fenc_row"):
+        return "fenc_row"
+    return kernel if kernel.startswith("dconv_apply_kernel") else kernel.split("<")[0]
+
+
+def _dconv_expected(kt, dt, C, nb, L, cin, rw, fenc_row):
+    """the (site, kernel family) labels of one encoder level's DConv as dconv_plan predicts them"""
+    if fenc_row and dt == "bf16" and not rw and kt.lib.kt_fenc_row_supported(cin, C, L):
+        return {("fenc_row", "fenc_row")}
+    p = kt.dconv_plan(1 if dt == "bf16" else 0, C, nb, L, rw)
+    assert p["ok"]
+    if p["valu"]:
+        return {(s, k) for s in ("dconv0", "dconv1") for k in ("dconv_c3_kernel", "dconv_c1_stats_kernel",
+                                                               "dconv_c1_apply_kernel")}
+    norm = {kt.NORM_MOM: "gn_gelu_mom", kt.NORM_BF16: "gn_gelu_bf16_kernel", kt.NORM_F32: "gn_gelu_kernel"}[p["norm"]]
+    exp = {("dconv.conv3", "dconv_conv3_kernel" if p["conv3_mfma"] else "gemm"), ("dconv.gn_gelu", norm),
+           ("dconv.conv1x1.apply", "dconv_apply_kernel<%d>" % C if p["apply_mfma"] else "gemm")}
+    if p["norm"] != kt.NORM_MOM:
+        exp.add(("dconv.conv1x1.stats", "gemm"))
+    if p["rewrite"]:
+        exp.add(("dconv.conv1x1.apply", "dconv_apply_kernel<%d,rewrite>" % C))
+    return exp
+
+
+@pytest.mark.parametrize("T,dt,fenc_row", [(T, dt, "1") for T in (4096, 33297, 300000) for dt in ("bf16", "f32")]
+                         + [(44100, "bf16", "0")])
+def test_encoder_dconv_runs_its_plan(models, monkeypatch, T, dt, fenc_row):
+    """What runs is what dconv_plan says: per encoder stage, the (call site, kernel family) labels of one profiled
+    forward (B = 1) equal the plan's for that level's (mode, C, nb, L): the VALU layer, or per pass the MFMA kernel or a
+    GEMM, the statistics GEMM exactly when the moments pass does not run, the rewrite GEMM exactly when the apply pass
+    did not take it, and fenc_row in place of all of it exactly where the fused level applies.  The shapes reach every
+    row of DESIGN.md's plan table (L = 4, 16, 33 ... 75000)."""
+    import kernel_refs as kr
+    import ktest as kt
+    from athd.synth import synthetic_batch
+    monkeypatch.setenv("ATHD_FENC_ROW", fenc_row)
+    m = models[dt]
+    wav = torch.as_tensor(synthetic_batch(1, T, seed0=5)).cuda()
+    m.profile_start("@sites")
+    try:
+        m(wav, "bass")
+    finally:
+        recs = m.profile_stop()
+    got = {}
+    for r in recs:
+        kernel, _, where = r["kernel"].partition("@")
+        stage, _, site = where.partition(".")
+        if site.startswith("dconv") or site == "fenc_row" or site.endswith(".rewrite"):
+            got.setdefault(stage, set()).add((site, _dconv_family(kernel)))
+    levels = kr.encoder_levels(T, 1)
+    assert set(got) == set(levels), sorted(got)
+    for stage, (C, nb, L, cin, rw) in levels.items():
+        exp = _dconv_expected(kt, dt, C, nb, L, cin, rw, fenc_row == "1")
+        fused_rewrite = exp == {("fenc_row", "fenc_row")} or any(k.endswith(",rewrite>") for _, k in exp)
+        if not fused_rewrite:
+            exp.add((stage[:4] + ".rewrite", "gemm"))
+        assert got[stage] == exp, (stage, sorted(got[stage]), sorted(exp))
+
+
 def test_reference_decoders_stage_f32(models, state_dict):
     """The reference-owned decoders pinned at their own stage on REFERENCE-made data.
 
