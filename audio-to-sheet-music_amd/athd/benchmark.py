@@ -12,7 +12,10 @@ Mirrors, name for name:
   * `compute_sdr` / `compute_sisdr` <- `benchmark.py:555-588`: one SDR / SI-SDR per stem over the (1, C*T) flatten
                                        (`athd_sdr` / `athd_sisdr`, fp64 sums on the device).
   * `TrackResult`, `evaluate_model_on_track`, `evaluate_model`, `aggregate_results`, `save_results`
-                                    <- `benchmark.py:618-888` (same JSON layout), minus plotting / wandb.
+                                    <- `benchmark.py:618-888` (same JSON layout), minus figures / wandb.
+                                       `plot_spectrograms=True` computes the arrays of the reference's all-stems
+                                       figure on the device (`athd.utils`) and saves them as `.npz` where the
+                                       reference saves the `.png` (`:691-737`).
 The MUSDB18 `.stem.mp4` decode (`load_track_stems`, :591-615) needs stempeg/ffmpeg, which are absent here; tracks
 come from `athd.musdb` (pre-decoded arrays) or from memory.
 """
@@ -210,11 +213,41 @@ def track_result(track_name: str, model_name: str, estimates: Dict[str, torch.Te
                        sisdr["vocals"], sum(sisdr.values()) / len(sisdr))
 
 
+def track_spectrograms(mixture: torch.Tensor, estimates: Dict[str, torch.Tensor],
+                       reference_stems: Dict[str, torch.Tensor]) -> dict:
+    """The all-stems spectrogram set of `benchmark.py:692-733`: every stem's estimate and reference trimmed to
+    their common length (`:693-701`), the mixture to the shortest estimate (`:703-705`)."""
+    from .utils import all_stems_spectrograms
+    est_p, ref_p = {}, {}
+    for stem in STEMS:
+        e, r = estimates[stem], torch.as_tensor(reference_stems[stem])
+        n = min(e.shape[-1], r.shape[-1])
+        est_p[stem], ref_p[stem] = e[:, :n], r[:, :n]
+    n = min(mixture.shape[-1], min(e.shape[-1] for e in est_p.values()))
+    return all_stems_spectrograms(mixture[:, :n], est_p, ref_p, SAMPLE_RATE)
+
+
+def spectrogram_path(output_dir, track_name: str, model_name: str) -> Path:
+    """`benchmark.py:724-735` with `.npz` for `.png`."""
+    safe = model_name.replace(" ", "_").replace("(", "").replace(")", "")
+    return Path(output_dir) / "spectrograms" / track_name.replace(" ", "_") / f"{safe}_all_stems.npz"
+
+
 def evaluate_model_on_track(model: OurModel, mixture: torch.Tensor, reference_stems: Dict[str, torch.Tensor],
-                            track_name: str) -> Tuple[TrackResult, Dict[str, torch.Tensor]]:
-    """`benchmark.py:637-739` without plotting: per stem SDR / SI-SDR on the common length."""
+                            track_name: str, plot_spectrograms: bool = False,
+                            output_dir=None) -> Tuple[TrackResult, Dict[str, torch.Tensor]]:
+    """`benchmark.py:637-739`: per stem SDR / SI-SDR on the common length.  plot_spectrograms=True also computes
+    the all-stems spectrogram arrays (no figure) and, with an `output_dir`, saves them at the reference's path."""
     est = model.separate_all(mixture)
-    return track_result(track_name, model.name, est, reference_stems), est
+    result = track_result(track_name, model.name, est, reference_stems)
+    if plot_spectrograms:
+        from .utils import all_stems_npz
+        data = track_spectrograms(mixture, est, reference_stems)
+        if output_dir is not None:
+            path = spectrogram_path(output_dir, track_name, model.name)
+            path.parent.mkdir(parents=True, exist_ok=True)
+            np.savez(path, **all_stems_npz(data))
+    return result, est
 
 
 def log_track(r: TrackResult, log: Callable[[str], None] = print) -> None:
@@ -225,13 +258,15 @@ def log_track(r: TrackResult, log: Callable[[str], None] = print) -> None:
 
 
 def evaluate_model(model: OurModel, tracks: Iterable[Tuple[str, torch.Tensor, Dict[str, torch.Tensor]]],
-                   log: Optional[Callable[[str], None]] = print) -> List[TrackResult]:
+                   log: Optional[Callable[[str], None]] = print, plot_spectrograms: bool = False,
+                   output_dir=None) -> List[TrackResult]:
     """`benchmark.py:742-781`: tracks = (name, mixture (2, T), {stem: (2, T)}); a failing track is reported and
-    skipped like the reference's try/except."""
+    skipped like the reference's try/except.  plot_spectrograms / output_dir: see evaluate_model_on_track."""
     results = []
     for name, mixture, refs in tracks:
         try:
-            r, _ = evaluate_model_on_track(model, mixture, refs, name)
+            r, _ = evaluate_model_on_track(model, mixture, refs, name, plot_spectrograms=plot_spectrograms,
+                                           output_dir=output_dir)
         except Exception as e:          # noqa: BLE001 - the reference skips a failing track (:777-779)
             if log:
                 log(f"  Error processing {name}: {e}")

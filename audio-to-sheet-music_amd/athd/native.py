@@ -59,6 +59,11 @@ lib.athd_spectrogram_frames.argtypes = [_c.c_int64]
 lib.athd_spectrogram_frames.restype = _c.c_int64
 lib.athd_spectrogram_db.argtypes = [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_void_p]
 lib.athd_spectrogram_db.restype = _c.c_int
+lib.athd_eval_spectrogram_scratch_bytes.argtypes = [_c.c_int]
+lib.athd_eval_spectrogram_scratch_bytes.restype = _c.c_size_t
+lib.athd_eval_spectrogram.argtypes = [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_float, _c.c_int,
+                                      _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]
+lib.athd_eval_spectrogram.restype = _c.c_int
 lib.athd_set_decode_items.argtypes = [_c.c_void_p, _c.c_int64]
 lib.athd_set_decode_items.restype = _c.c_int
 lib.athd_profile_start.argtypes = [_c.c_void_p, _c.c_char_p]
@@ -79,8 +84,8 @@ EXPORTED = ["athd_version", "athd_create", "athd_set_weight", "athd_num_required
             "athd_finalize", "athd_set_decode_items", "athd_workspace_bytes", "athd_forward", "athd_forward_prompts",
             "athd_num_windows", "athd_overlap_add", "athd_overlap_add_weighted", "athd_ola_normalize", "athd_sdr",
             "athd_sisdr", "athd_resample_length", "athd_resample_scratch_bytes", "athd_resample",
-            "athd_spectrogram_frames", "athd_spectrogram_db", "athd_profile_start",
-            "athd_profile_stop", "athd_profile_count", "athd_profile_get", "athd_last_error", "athd_destroy"]
+            "athd_spectrogram_frames", "athd_spectrogram_db", "athd_eval_spectrogram_scratch_bytes",
+            "athd_eval_spectrogram", "athd_profile_start", "athd_profile_stop", "athd_profile_count", "athd_profile_get", "athd_last_error", "athd_destroy"]
 
 F32, BF16 = 0, 1
 

@@ -140,7 +140,7 @@ const std::vector<std::pair<std::string, std::vector<int64_t>>>& keys() {
 // =============================================================================================== ABI
 extern "C" {
 
-int athd_version(void) { return 102; }
+int athd_version(void) { return 103; }
 
 int athd_num_required_keys(void) { return (int)keys().size(); }
 
@@ -542,6 +542,16 @@ int64_t athd_spectrogram_frames(int64_t T) { return spectrogram_frames(T); }
 int athd_spectrogram_db(const float* wav, int channels, int64_t T, float* out, void* stream) {
     const int rc = spectrogram_db_launch(wav, channels, T, out, (hipStream_t)stream);
     return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : ATHD_EHIP);
+}
+
+size_t athd_eval_spectrogram_scratch_bytes(int n_signals) { return eval_spectrogram_scratch_bytes(n_signals); }
+
+int athd_eval_spectrogram(const float* wav, int n_signals, int channels, int64_t T, int64_t signal_stride, float power,
+                          int to_db, float top_db, float* out, float* range, void* scratch, size_t scratch_bytes,
+                          void* stream) {
+    const int rc = eval_spectrogram_launch(wav, n_signals, channels, T, signal_stride, power, to_db, top_db, out, range,
+                                           scratch, scratch_bytes, (hipStream_t)stream);
+    return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : (rc == -5 ? ATHD_EWORKSPACE : ATHD_EHIP));
 }
 
 int athd_profile_start(athd_ctx* c, const char* kernel) {

@@ -11,6 +11,10 @@
 //
 // Spectrogram = torch.stft(mean of the channels, n_fft = 2048, hop_length = 512) with torch's defaults (rectangular
 // window, center = True, reflect pad 1024, one-sided), 20 log10(|X| + 1e-8), frequency-major (1025, 1 + T / 512).
+//
+// Evaluation spectrogram = utils.compute_spectrogram (utils.py:30-95) of benchmark.py --plot-spectrograms and
+// generate_spectrogram.py: the same framing with a periodic Hann window, |X|^power, 10 log10(max(., 1e-10)) and a floor
+// at the array's maximum - top_db, for several signals per call.
 #include <cmath>
 #include <cstring>
 #include <map>
@@ -380,6 +384,201 @@ int spectrogram_db_launch(const float* wav, int channels, int64_t T, float* out,
     if (ks.on())
         ks.begin("spectrogram_db_kernel", (double)F * 5.0 * SP_M * 10.0, ((double)T * channels + (double)F * SP_BINS) * 4);
     hipLaunchKernelGGL(spectrogram_db_kernel, dim3((unsigned)gx), dim3(256), 0, s, wav, channels, T, F, out);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------- evaluation spectrogram
+// utils.compute_spectrogram (utils.py:30-95): periodic Hann window, |X|^power, 10 log10(max(., 1e-10)) and the floor
+// max(dB, max over the signal's array - top_db).  Pass 1 writes the unclamped values and reduces each signal's
+// maximum and minimum into its scratch slot; pass 2 clamps in place and writes the range.
+//
+// Scratch slot of a signal = {enc(max), ~enc(min)}, both zeroed per call and raised with atomicMax on unsigned.
+// enc is the order-preserving map of a float onto unsigned (sign bit flipped for non-negative values, every bit for
+// negative ones), so the result is the exact fp32 extreme whatever the order of arrival.  0 is below enc of every
+// value, -inf included.
+ATHD_DEV unsigned ev_enc(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+ATHD_DEV float ev_dec(unsigned e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e); }
+
+constexpr int EV_P2 = 1, EV_DB = 2;           // mode bits of eval_spectrogram_kernel
+
+// spectrogram_db_kernel's frame-group FFT (its body is repeated here so that its machine code stays as it is) with
+// the Hann factor applied on load: w[n] = 0.5 - 0.5 cos(2 pi n / 2048) and cos(2 pi n / 2048) = Re W2048^n is tw's
+// real part.  Grid (frame group, signal).
+__global__ __launch_bounds__(256) void eval_spectrogram_kernel(const float* __restrict__ wav_all, int C, int64_t T,
+                                                               int64_t F, int64_t sig_stride, int mode,
+                                                               float* __restrict__ out_all,
+                                                               unsigned* __restrict__ slots) {
+    __shared__ float2 tw[SP_M];
+    __shared__ float2 zb[SP_M + SP_M / 8];
+    __shared__ float stage[SP_BINS * SP_ROW];
+    __shared__ float red[8];
+    const int j = threadIdx.x;
+    const float* wav = wav_all + (int64_t)blockIdx.y * sig_stride;
+    float* out = out_all + (int64_t)blockIdx.y * SP_BINS * F;
+    for (int m = j; m < SP_M; m += 256) {
+        double sn, cs;
+        sincospi(-(double)m / 1024.0, &sn, &cs);
+        tw[m] = make_float2((float)cs, (float)sn);
+    }
+    __syncthreads();
+    const int64_t f0 = (int64_t)blockIdx.x * SP_FB;
+    const int nfb = (int)(F - f0 < SP_FB ? F - f0 : SP_FB);
+    const float inv_c = 1.0f / (float)C;
+    for (int fb = 0; fb < nfb; ++fb) {
+        float2 v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float e[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int n = 2 * (j + 256 * r) + h;
+                int64_t p = (f0 + fb) * SP_HOP + n - SP_NFFT / 2;
+                p = p < 0 ? -p : (p >= T ? 2 * (T - 1) - p : p);           // reflect (T > 1024: one fold)
+                float a = wav[p];
+                if (C > 1) {
+                    for (int ch = 1; ch < C; ++ch) a += wav[(int64_t)ch * T + p];
+                    a = C == 2 ? a * 0.5f : a * inv_c;
+                }
+                e[h] = a * (0.5f - 0.5f * sp_tw(tw, n).x);
+            }
+            v[r] = make_float2(e[0], e[1]);
+        }
+#pragma unroll
+        for (int pass = 0; pass < 5; ++pass) {
+            const int Ns = 1 << (2 * pass);
+            const int k = j & (Ns - 1);
+            if (pass > 0) {
+#pragma unroll
+                for (int r = 1; r < 4; ++r) v[r] = sp_cmul(v[r], sp_tw(tw, r * k * (512 / Ns)));
+            }
+            const float2 a0 = make_float2(v[0].x + v[2].x, v[0].y + v[2].y);
+            const float2 a1 = make_float2(v[0].x - v[2].x, v[0].y - v[2].y);
+            const float2 a2 = make_float2(v[1].x + v[3].x, v[1].y + v[3].y);
+            const float2 a3 = make_float2(v[1].y - v[3].y, v[3].x - v[1].x);    // -i (v1 - v3)
+            const int j0 = (j / Ns) * 4 * Ns + k;
+            zb[sp_slot(j0)] = make_float2(a0.x + a2.x, a0.y + a2.y);
+            zb[sp_slot(j0 + Ns)] = make_float2(a1.x + a3.x, a1.y + a3.y);
+            zb[sp_slot(j0 + 2 * Ns)] = make_float2(a0.x - a2.x, a0.y - a2.y);
+            zb[sp_slot(j0 + 3 * Ns)] = make_float2(a1.x - a3.x, a1.y - a3.y);
+            __syncthreads();
+            if (pass < 4) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = zb[sp_slot(j + 256 * r)];
+                __syncthreads();
+            }
+        }
+        for (int k = j; k <= SP_M; k += 256) {
+            const float2 a = zb[sp_slot(k & 1023)];
+            const float2 bq = zb[sp_slot((SP_M - k) & 1023)];
+            const float2 b = make_float2(bq.x, -bq.y);
+            const float2 ev = make_float2(0.5f * (a.x + b.x), 0.5f * (a.y + b.y));
+            const float2 od = make_float2(0.5f * (a.y - b.y), -0.5f * (a.x - b.x));    // -i (a - b) / 2
+            const float2 wo = sp_cmul(sp_tw(tw, k), od);
+            // |X|^power, the log and the factor 10 in double on the fp32 spectrum, rounded once
+            const double re = (double)(ev.x + wo.x), im = (double)(ev.y + wo.y);
+            const double p2 = re * re + im * im;
+            const double S = (mode & EV_P2) ? p2 : sqrt(p2);
+            stage[k * SP_ROW + fb] = (float)((mode & EV_DB) ? 10.0 * log10(S > 1e-10 ? S : 1e-10) : S);
+        }
+        __syncthreads();
+    }
+    float mx = -INFINITY, mn = INFINITY;
+    for (int e = j; e < SP_BINS * SP_FB; e += 256) {
+        const int k = e / SP_FB, fb = e % SP_FB;
+        if (fb < nfb) {
+            const float val = stage[k * SP_ROW + fb];
+            out[(int64_t)k * F + f0 + fb] = val;
+            mx = fmaxf(mx, val);
+            mn = fminf(mn, val);
+        }
+    }
+    // workgroup extremes: wave shuffles, then the 4 waves through LDS; one atomic pair per workgroup
+    mx = wave_max(mx);
+    mn = -wave_max(-mn);
+    if ((j & 63) == 0) {
+        red[j >> 6] = mx;
+        red[4 + (j >> 6)] = mn;
+    }
+    __syncthreads();
+    if (j == 0) {
+        mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+        mn = fminf(fminf(red[4], red[5]), fminf(red[6], red[7]));
+        atomicMax(slots + 2 * blockIdx.y, ev_enc(mx));
+        atomicMax(slots + 2 * blockIdx.y + 1, ~ev_enc(mn));
+    }
+}
+
+// In-place max(value, M - top_db) over a signal's n values, M and the minimum from its scratch slot; range (may be
+// null) = {min, max} of the clamped array (the clamp is monotone, so they follow from the slot).  Grid (chunk,
+// signal); a signal's slab starts on a 4-byte boundary only (n is odd), so the scalars before the first 16-byte
+// boundary and after the last whole float4 go to the first threads of chunk 0.  clamp == 0: range only.
+__global__ __launch_bounds__(256) void db_floor_kernel(float* __restrict__ out_all, int64_t n, float top_db, int clamp,
+                                                       const unsigned* __restrict__ slots, float* __restrict__ range) {
+    const int sig = blockIdx.y;
+    const float M = ev_dec(slots[2 * sig]);
+    const float lowest = ev_dec(~slots[2 * sig + 1]);
+    const float floor_db = M - top_db;
+    if (range && blockIdx.x == 0 && threadIdx.x == 0) {
+        range[2 * sig] = clamp ? fmaxf(lowest, floor_db) : lowest;
+        range[2 * sig + 1] = M;
+    }
+    if (!clamp) return;
+    float* p = out_all + (int64_t)sig * n;
+    int64_t head = (int64_t)(((16 - ((uintptr_t)p & 15)) & 15) >> 2);
+    if (head > n) head = n;
+    const int64_t nv = (n - head) / 4;
+    float4* pv = (float4*)(p + head);
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < nv; g += (int64_t)gridDim.x * 256) {
+        float4 q = pv[g];
+        q.x = fmaxf(q.x, floor_db);
+        q.y = fmaxf(q.y, floor_db);
+        q.z = fmaxf(q.z, floor_db);
+        q.w = fmaxf(q.w, floor_db);
+        pv[g] = q;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 8) {                  // at most 3 head and 3 tail scalars
+        const int t = threadIdx.x;
+        const int64_t idx = t < 4 ? (int64_t)t : head + nv * 4 + (t - 4);
+        if (t < 4 ? idx < head : idx < n) p[idx] = fmaxf(p[idx], floor_db);
+    }
+}
+
+size_t eval_spectrogram_scratch_bytes(int n_signals) { return n_signals > 0 ? (size_t)n_signals * 8 : 0; }
+
+// -1: bad argument, -5: scratch too small, > 0: HIP error
+int eval_spectrogram_launch(const float* wav, int n_signals, int channels, int64_t T, int64_t signal_stride,
+                            float power, int to_db, float top_db, float* out, float* range, void* scratch,
+                            size_t scratch_bytes, hipStream_t s) {
+    if (!wav || !out || !scratch || n_signals <= 0 || n_signals > 65535 || channels <= 0 || T <= SP_NFFT / 2) return -1;
+    if (!(power == 1.0f || power == 2.0f) || !(top_db >= 0.0f)) return -1;                 // NaN fails the comparison
+    if (channels > INT64_MAX / T || signal_stride < (int64_t)channels * T) return -1;
+    const int64_t F = spectrogram_frames(T);
+    const int64_t gx = (F + SP_FB - 1) / SP_FB;
+    if (gx > 0x7fffffff) return -1;
+    if (scratch_bytes < eval_spectrogram_scratch_bytes(n_signals)) return -5;
+    const int64_t n = F * SP_BINS;
+    const int clamp = to_db && !std::isinf(top_db);
+    HIP_CHECK_RET(hipMemsetAsync(scratch, 0, eval_spectrogram_scratch_bytes(n_signals), s));
+    {
+        KScope ks(s);
+        // HBM-bound like spectrogram_db_kernel: every signal read once, its array written once
+        if (ks.on())
+            ks.begin("eval_spectrogram_kernel", (double)n_signals * F * 5.0 * SP_M * 10.0,
+                     (double)n_signals * ((double)T * channels + (double)n) * 4);
+        hipLaunchKernelGGL(eval_spectrogram_kernel, dim3((unsigned)gx, (unsigned)n_signals), dim3(256), 0, s, wav,
+                           channels, T, F, signal_stride, (power == 2.0f ? EV_P2 : 0) | (to_db ? EV_DB : 0), out,
+                           (unsigned*)scratch);
+        HIP_CHECK_RET(hipGetLastError());
+    }
+    if (!clamp && !range) return 0;
+    KScope ks(s);
+    if (ks.on()) ks.begin("db_floor_kernel", 0.0, clamp ? (double)n_signals * 2.0 * n * 4 : (double)n_signals * 16);
+    const int64_t chunks = clamp ? std::min<int64_t>(4096, (n / 4 + 1023) / 1024) : 1;      // ~4 float4 per thread
+    hipLaunchKernelGGL(db_floor_kernel, dim3((unsigned)std::max<int64_t>(1, chunks), (unsigned)n_signals), dim3(256), 0,
+                       s, out, n, top_db, clamp, (const unsigned*)scratch, range);
     return (int)hipGetLastError();
 }
 

@@ -260,5 +260,11 @@ int resample_launch(const float* in, int64_t L, int in_ch, int64_t fs, int64_t c
                     int out_ch, void* scratch, size_t scratch_bytes, hipStream_t s);
 int64_t spectrogram_frames(int64_t T);
 int spectrogram_db_launch(const float* wav, int channels, int64_t T, float* out, hipStream_t s);
+// evaluation spectrograms of utils.py:30-95 (Hann, |X|^power, dB with the top_db floor), n_signals per call;
+// eval_spectrogram_launch returns -1 (bad argument), -5 (scratch too small) or a HIP error
+size_t eval_spectrogram_scratch_bytes(int n_signals);
+int eval_spectrogram_launch(const float* wav, int n_signals, int channels, int64_t T, int64_t signal_stride,
+                            float power, int to_db, float top_db, float* out, float* range, void* scratch,
+                            size_t scratch_bytes, hipStream_t s);
 
 }  // namespace athd

@@ -166,6 +166,34 @@ int athd_resample(const float* in, int64_t length, int in_channels, int64_t fram
 int64_t athd_spectrogram_frames(int64_t T);
 int athd_spectrogram_db(const float* wav, int channels, int64_t T, float* out, void* stream);
 
+/* ---- Evaluation spectrograms: utils.compute_spectrogram / amplitude_to_db (utils.py:30-95), as benchmark.py
+ * --plot-spectrograms and generate_spectrogram.py compute them, for n_signals signals of equal shape in one call ----
+ * Stream-only like the audio front end: no context, no host synchronisation, no allocation; a scratch
+ * initialisation and two kernels on `stream`, capturable in a graph from the first call.
+ *
+ * Per signal i (the planar (channels, T) f32 block at wav + i * signal_stride, signal_stride >= channels * T):
+ *   mono = mean of the channels (one channel is used as is);
+ *   X = torch.stft(mono, n_fft = 2048, hop_length = 512, window = torch.hann_window(2048), center = True, reflect
+ *       pad of 1024, one-sided), window w[n] = 0.5 - 0.5 cos(2 pi n / 2048);
+ *   S = |X|^power, power 1.0 or 2.0;
+ *   to_db == 0: the result is S.  Otherwise dB = 10 log10(max(S, 1e-10)) and the result is max(dB, M - top_db) with
+ *   M the maximum of dB over the signal's whole array; top_db = INFINITY leaves every value unchanged.
+ * out: device (n_signals, 1025, athd_spectrogram_frames(T)) f32, frequency-major.  range: device (n_signals, 2) f32 =
+ * {min, max} of each signal's result, or NULL.  scratch: device, athd_eval_spectrogram_scratch_bytes(n_signals) bytes.
+ *
+ * Rounding: the FFT runs in fp32; S, the logarithm and the factor 10 are evaluated in double on that spectrum and
+ * rounded once to fp32; M is the maximum of those fp32 values (an integer maximum over an order-preserving encoding,
+ * so it does not depend on the order of arrival); M - top_db is one fp32 subtraction and the clamp an fp32 max.  A
+ * signal's result depends neither on the other signals of the call nor on the run.
+ *
+ * ATHD_EINVAL: T <= 1024, channels <= 0, n_signals <= 0 or > 65535, power not 1 or 2, top_db negative or NaN, a null
+ * wav / out / scratch, signal_stride < channels * T, more than 2^31 - 1 groups of 8 frames.  ATHD_EWORKSPACE: scratch
+ * too small.  Nothing is written in either case. */
+size_t athd_eval_spectrogram_scratch_bytes(int n_signals);
+int athd_eval_spectrogram(const float* wav, int n_signals, int channels, int64_t T, int64_t signal_stride,
+                          float power, int to_db, float top_db, float* out, float* range, void* scratch,
+                          size_t scratch_bytes, void* stream);
+
 /* Kernel timing (measurement aid for bench.py; not part of the reference interface).  Between
  * athd_profile_start and athd_profile_stop every launch of kernel `kernel` (its rocprofv3 symbol without
  * "void athd::", the argument list and 'u' suffixes, e.g. "attn_kernel<0>"; NULL or "" = all kernels) made
