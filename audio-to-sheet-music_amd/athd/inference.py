@@ -28,7 +28,8 @@ from .weights import STEMS
 
 
 def load_model(checkpoint_path: str, device: str = "cuda", dtype: str = "bf16",
-               text_table: Optional[Dict[str, np.ndarray]] = None, clap=None, tokenizer=None) -> AudioTextHTDemucs:
+               text_table: Optional[Dict[str, np.ndarray]] = None, clap=None, tokenizer=None,
+               native_text: bool = False) -> AudioTextHTDemucs:
     """`test_inference.py:21-40`.  The checkpoint is read with `torch.load(weights_only=True)` (no unpickling of
     code); `checkpoint["model_state_dict"]` is loaded non-strictly.  The pretrained htdemucs object of the reference
     is not needed: every `htdemucs.*` key the hot path uses is in the checkpoint, as the reference's own
@@ -36,7 +37,25 @@ def load_model(checkpoint_path: str, device: str = "cuda", dtype: str = "bf16",
     (see athd/text.py).  With neither given, CLAP and its tokenizer are built from `laion/clap-htsat-unfused` in the
     local Hugging Face cache as the reference does (`:26-28`, `text.load_clap`, `local_files_only=True`), the
     checkpoint's `clap.*` keys are loaded into it (`:34-35`), and the embeddings of the 4 stem prompts are computed
-    once and cached (the CLAP tower is frozen: its output depends on the prompt string only)."""
+    once and cached (the CLAP tower is frozen: its output depends on the prompt string only).
+    `native_text=True`: the text tower runs in libathd.so, built from the checkpoint's `clap.text_model.*` /
+    `clap.text_projection.*` keys (`get_text_features` rows, the reference's ClapModel branch); only `tokenizer=` is
+    needed, and a checkpoint without those keys is an error."""
+    if native_text:
+        if tokenizer is None or clap is not None or text_table is not None:
+            raise ValueError("load_model(native_text=True) takes tokenizer= alone (no clap=, no text_table=): the "
+                             "tower's weights come from the checkpoint")
+        ckpt = torch.load(checkpoint_path, map_location="cpu", weights_only=True)
+        sd = ckpt["model_state_dict"] if isinstance(ckpt, dict) and "model_state_dict" in ckpt else ckpt
+        if not any(k.startswith(("clap.text_model.", "module.clap.text_model.")) for k in sd):
+            raise RuntimeError(f"load_model(native_text=True): checkpoint {checkpoint_path} has no clap.text_model.* / "
+                               f"clap.text_projection.* keys to build the text tower from; pass clap=/tokenizer= or "
+                               f"text_table= instead")
+        model = AudioTextHTDemucs(None, None, tokenizer, dtype=dtype, native_text=True)
+        model.load_state_dict(sd, strict=False)       # a partial tower raises, listing the missing keys
+        model = model.to(device)
+        model.eval()
+        return model
     if text_table is None and (clap is None) != (tokenizer is None):
         # the reference builds the two together (`:26-28`); a lone tokenizer must not be silently replaced by the
         # cached one, nor a lone model be left without one (ADVICE r05)

@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Union
 import numpy as np
 import torch
 
-from .text import PromptEmbedder
+from .text import NativeClapText, PromptEmbedder
 from .weights import hot_path_spec
 
 
@@ -32,7 +32,8 @@ class AudioTextHTDemucs:
     def __init__(self, htdemucs_model=None, clap_encoder=None, clap_tokenizer=None, model_dim: int = 384,
                  text_dim: int = 512, num_heads: int = 8, sample_rate: int = 44100, segment: float = 7.8,
                  dtype: str = "bf16", text_table: Optional[Dict[str, np.ndarray]] = None,
-                 decode_items: Optional[int] = None):
+                 decode_items: Optional[int] = None, native_text: bool = False,
+                 native_text_dtype: str = "f32", clap_source: Optional[str] = None):
         if (model_dim, text_dim, num_heads) != (384, 512, 8):
             raise ValueError("the native path is built for model_dim=384, text_dim=512, num_heads=8 "
                              "(config.yaml:15-17)")
@@ -44,7 +45,13 @@ class AudioTextHTDemucs:
         # (segment, prompt) items per decode chunk (athd_set_decode_items; None = the library default, 64).  256 puts
         # a 64-segment x 4-prompt batch in one chunk (≈49 GB at round 3: athd_workspace_bytes, reported by bench.py as workspace_gb).
         self.decode_items = decode_items
-        self.embedder = PromptEmbedder(clap_encoder, clap_tokenizer, text_table)
+        # native_text: prompt embeddings from libathd.so's CLAP text tower (athd/text.py NativeClapText), built from the
+        # checkpoint's clap.text_model.* / clap.text_projection.* keys; only a tokenizer is needed.  clap_source: the
+        # class the checkpoint's `clap` was ("ClapModel", the default, or "ClapTextModelWithProjection") when no
+        # `clap_encoder` is attached to tell.
+        native = NativeClapText(dtype=native_text_dtype) if native_text else None
+        self.embedder = PromptEmbedder(clap_encoder, clap_tokenizer, text_table, native=native,
+                                       native_source=clap_source)
         self._weights: Dict[str, np.ndarray] = {}
         if htdemucs_model is not None:
             for k, v in htdemucs_model.state_dict().items():
@@ -58,7 +65,8 @@ class AudioTextHTDemucs:
     def load_state_dict(self, state_dict, strict: bool = False):
         """Reference key names; like `load_state_dict(strict=False)` unknown keys (htdemucs.decoder.*, ...) are
         ignored.  `clap.*` keys are loaded into the attached CLAP model (non-strictly, as the reference's submodule)
-        when there is one, and ignored otherwise.  Returns (missing_keys, unexpected_keys) restricted to the hot-path
+        when there is one, into the native text tower with `native_text=True` (its `clap.text_model.*` /
+        `clap.text_projection.*` keys; a partial set raises), and ignored otherwise.  Returns (missing_keys, unexpected_keys) restricted to the hot-path
         contract."""
         needed = {k for k, _, _ in hot_path_spec()}
         unexpected = []
@@ -72,7 +80,13 @@ class AudioTextHTDemucs:
                 if k.startswith("clap."):     # the reference's self.clap submodule (ATHTDemucs_v2.py:165)
                     clap_state[k[len("clap."):]] = v
                 unexpected.append(k)
-        if self.embedder.load_clap_state(clap_state):
+        native = self.embedder.native
+        n_clap = self.embedder.load_clap_state(clap_state)
+        if native is not None and native.loaded:
+            from .weights import clap_text_spec
+            tower = {"clap." + k for k, _, _ in clap_text_spec()}
+            unexpected = [k for k in unexpected if k not in tower]
+        if n_clap:
             loaded = set(self.embedder.clap.state_dict())
             unexpected = [k for k in unexpected
                           if not (k.startswith("clap.") and k[len("clap."):] in loaded)]
@@ -91,6 +105,8 @@ class AudioTextHTDemucs:
         if self.device != device:
             self._ctx = None
         self.device = device
+        if self.embedder.native is not None:
+            self.embedder.native.to(device)
         return self
 
     def cuda(self, index: int = 0):

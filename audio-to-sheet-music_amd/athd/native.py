@@ -75,6 +75,24 @@ lib.athd_profile_count.restype = _c.c_int
 lib.athd_profile_get.argtypes = [_c.c_void_p, _c.c_int, _c.POINTER(_c.c_char_p), _c.POINTER(_c.c_longlong),
                                  _c.POINTER(_c.c_double), _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]
 lib.athd_profile_get.restype = _c.c_int
+lib.athd_text_create.argtypes = [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_int]
+lib.athd_text_create.restype = _c.c_int
+lib.athd_text_set_weight.argtypes = [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int, _c.c_int]
+lib.athd_text_set_weight.restype = _c.c_int
+lib.athd_text_num_required_keys.restype = _c.c_int
+lib.athd_text_required_key.argtypes = [_c.c_int]
+lib.athd_text_required_key.restype = _c.c_char_p
+lib.athd_text_finalize.argtypes = [_c.c_void_p]
+lib.athd_text_finalize.restype = _c.c_int
+lib.athd_text_workspace_bytes.argtypes = [_c.c_void_p, _c.c_int, _c.c_int]
+lib.athd_text_workspace_bytes.restype = _c.c_size_t
+lib.athd_text_encode.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                 _c.c_void_p, _c.c_size_t, _c.c_void_p]
+lib.athd_text_encode.restype = _c.c_int
+lib.athd_text_last_error.argtypes = [_c.c_void_p]
+lib.athd_text_last_error.restype = _c.c_char_p
+lib.athd_text_destroy.argtypes = [_c.c_void_p]
+lib.athd_text_destroy.restype = None
 lib.athd_last_error.argtypes = [_c.c_void_p]
 lib.athd_last_error.restype = _c.c_char_p
 lib.athd_destroy.argtypes = [_c.c_void_p]
@@ -85,7 +103,10 @@ EXPORTED = ["athd_version", "athd_create", "athd_set_weight", "athd_num_required
             "athd_num_windows", "athd_overlap_add", "athd_overlap_add_weighted", "athd_ola_normalize", "athd_sdr",
             "athd_sisdr", "athd_resample_length", "athd_resample_scratch_bytes", "athd_resample",
             "athd_spectrogram_frames", "athd_spectrogram_db", "athd_eval_spectrogram_scratch_bytes",
-            "athd_eval_spectrogram", "athd_profile_start", "athd_profile_stop", "athd_profile_count", "athd_profile_get", "athd_last_error", "athd_destroy"]
+            "athd_eval_spectrogram", "athd_profile_start", "athd_profile_stop", "athd_profile_count", "athd_profile_get", "athd_last_error", "athd_destroy",
+            "athd_text_create", "athd_text_set_weight", "athd_text_num_required_keys", "athd_text_required_key",
+            "athd_text_finalize", "athd_text_workspace_bytes", "athd_text_encode", "athd_text_last_error",
+            "athd_text_destroy"]
 
 F32, BF16 = 0, 1
 
@@ -158,6 +179,54 @@ class Context:
     def close(self):
         if getattr(self, "h", None):
             lib.athd_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def text_required_keys():
+    return [lib.athd_text_required_key(i).decode() for i in range(lib.athd_text_num_required_keys())]
+
+
+class TextContext:
+    """Owns one athd_text_ctx (the CLAP text tower's packed weights on one device)."""
+
+    def __init__(self, device: int = 0, dtype: int = F32):
+        h = _c.c_void_p()
+        rc = lib.athd_text_create(_c.byref(h), int(device), int(dtype))
+        if rc != 0:
+            raise AthdError(f"athd_text_create failed ({rc}) on device {device}")
+        self.h = h
+        self.device = device
+        self.dtype = dtype
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise AthdError(f"{what} failed ({rc}): {lib.athd_text_last_error(self.h).decode()}")
+
+    def set_weight(self, key: str, arr):
+        a = np.ascontiguousarray(np.asarray(arr, dtype=np.float32))
+        shape = (_c.c_int64 * max(a.ndim, 1))(*a.shape)
+        self._check(lib.athd_text_set_weight(self.h, key.encode(), a.ctypes.data_as(_c.c_void_p), shape, a.ndim, 0),
+                    f"text_set_weight({key})")
+
+    def finalize(self):
+        self._check(lib.athd_text_finalize(self.h), "athd_text_finalize")
+
+    def workspace_bytes(self, P: int, L: int) -> int:
+        return int(lib.athd_text_workspace_bytes(self.h, P, L))
+
+    def encode(self, ids_ptr, mask_ptr, P, L, normalize, out_ptr, ws_ptr, ws_bytes, stream_ptr):
+        self._check(lib.athd_text_encode(self.h, ids_ptr, mask_ptr, P, L, int(bool(normalize)), out_ptr, ws_ptr,
+                                         ws_bytes, stream_ptr), "athd_text_encode")
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.athd_text_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -183,6 +183,52 @@ def synthetic_text_table(n: int = 4, seed: int = 7, dim: int = TEXT_DIM) -> np.n
     return t.astype(np.float32)
 
 
+def clap_text_spec():
+    """[(key, shape, kind)] of the CLAP text tower (Hugging Face names, as a reference checkpoint carries them under
+    `clap.`): RoBERTa-base, the pooler and the 768 -> 512 -> 512 projection; 203 float tensors (the contract of
+    `athd_text_set_weight`, include/athd.h)."""
+    H, F, P = 768, 3072, 512
+    e = "text_model.embeddings."
+    spec = [(e + "word_embeddings.weight", (50265, H), "emb"), (e + "position_embeddings.weight", (514, H), "emb"),
+            (e + "token_type_embeddings.weight", (1, H), "emb"),
+            (e + "LayerNorm.weight", (H,), "gn_w"), (e + "LayerNorm.bias", (H,), "gn_b")]
+
+    def lin(p, n, k, kind="lin"):
+        return [(p + ".weight", (n, k), kind), (p + ".bias", (n,), "bias")]
+
+    def ln(p):
+        return [(p + ".weight", (H,), "gn_w"), (p + ".bias", (H,), "gn_b")]
+
+    for i in range(12):
+        p = f"text_model.encoder.layer.{i}."
+        spec += lin(p + "attention.self.query", H, H, "lin_qk") + lin(p + "attention.self.key", H, H, "lin_qk")
+        spec += lin(p + "attention.self.value", H, H) + lin(p + "attention.output.dense", H, H)
+        spec += ln(p + "attention.output.LayerNorm")
+        spec += lin(p + "intermediate.dense", F, H) + lin(p + "output.dense", H, F) + ln(p + "output.LayerNorm")
+    spec += lin("text_model.pooler.dense", H, H) + lin("text_projection.linear1", P, H)
+    spec += lin("text_projection.linear2", P, P)
+    return spec
+
+
+def synthetic_clap_text_state_dict(seed: int = 0) -> "OrderedDict[str, np.ndarray]":
+    """Seeded full-size weights of the CLAP text tower (`clap_text_spec`), drawn as float32 from numpy PCG64 seeded
+    with ``seed`` xor crc32(key) per key.  Matrix weights N(0,1) / sqrt(fan_in), the query and key weights twice
+    that (so that attention is not uniform), biases 0.1 N(0,1), LayerNorm weights 1 + 0.1 N(0,1) and biases
+    0.1 N(0,1), embedding tables N(0,1)."""
+    sd = OrderedDict()
+    for key, shape, kind in clap_text_spec():
+        rng = np.random.Generator(np.random.PCG64((seed ^ zlib.crc32(key.encode())) & 0xFFFFFFFF))
+        w = rng.standard_normal(size=shape, dtype=np.float32)
+        if kind in ("lin", "lin_qk"):
+            w *= np.float32((2.0 if kind == "lin_qk" else 1.0) / np.sqrt(shape[1]))
+        elif kind in ("bias", "gn_b"):
+            w *= np.float32(0.1)
+        elif kind == "gn_w":
+            w = np.float32(1.0) + np.float32(0.1) * w
+        sd[key] = np.ascontiguousarray(w, dtype=np.float32)
+    return sd
+
+
 STEMS = ["drums", "bass", "other", "vocals"]          # test_inference.py:18
 
 

@@ -9,6 +9,7 @@
 #include "ctx.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "text_tower.h"
 
 namespace athd {   // norm.hip, dec_last.hip, fdec1f.hip: the tuning constants next to their launchers
 int dec_merge_run();
@@ -349,6 +350,38 @@ int kt_gn_apply(float* x, int64_t nb, int64_t N, int64_t C, const double* stats,
                 void* stream) {
     gn_apply_launch(x, (int)nb, N, (int)C, stats, w, b, (hipStream_t)stream);
     return (int)hipGetLastError();
+}
+
+// ---- the CLAP text tower's kernels (text_tower.hip; tests/ktest_text.py) ----
+struct KtTtGemm {
+    void* W; int64_t bf16; void* X; int64_t ldx, M, N, K; void* bias; void* res; int64_t ldr, act; void* part; void* out;
+    int64_t ldo;
+};
+struct KtTtAttn { void* part; int64_t S; void* bias; void* mask; int64_t P, L; void* out; };
+int64_t kt_sizeof_tt_gemm() { return (int64_t)sizeof(KtTtGemm); }
+int64_t kt_sizeof_tt_attn() { return (int64_t)sizeof(KtTtAttn); }
+// {S, W, KW} of the (N, K) shape's plan; 0 if the shape has none
+int64_t kt_tt_gemm_plan(int64_t N, int64_t K, int64_t* out3) {
+    const TtGemmPlan* p = tt_gemm_plan((int)N, (int)K);
+    if (!p) return 0;
+    out3[0] = p->S; out3[1] = p->W; out3[2] = p->KW;
+    return 1;
+}
+// the skinny GEMM with its slice reduction: out = act(X W^T + bias (+ res)); part: S * M * N floats
+int kt_tt_gemm(const KtTtGemm* d, void* stream) {
+    const TtGemmPlan* p = tt_gemm_plan((int)d->N, (int)d->K);
+    if (!p) return -1;
+    int rc = tt_gemm_launch(d->bf16 != 0, d->W, (const float*)d->X, d->ldx, (int)d->M, *p, (float*)d->part,
+                            (hipStream_t)stream);
+    if (rc != 0) return rc;
+    return tt_reduce_launch((const float*)d->part, p->S, (int)d->M, p->N, (const float*)d->bias, (const float*)d->res,
+                            d->ldr, (int)d->act, (float*)d->out, d->ldo, (hipStream_t)stream);
+}
+int kt_tt_attn(const KtTtAttn* d, void* stream) {
+    int rc = tt_init();
+    if (rc != 0) return rc;
+    return tt_attn_launch((const float*)d->part, (int)d->S, (const float*)d->bias, (const int32_t*)d->mask, (int)d->P,
+                          (int)d->L, (float*)d->out, (hipStream_t)stream);
 }
 
 }  // extern "C"

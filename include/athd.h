@@ -5,8 +5,9 @@
  *   AudioTextHTDemucs(htdemucs, clap, tokenizer)          /root/reference/src/models/stem_separation/ATHTDemucs_v2.py:151-188
  *   model.load_state_dict(ckpt["model_state_dict"], strict=False)   test_inference.py:34-35
  *   model.forward(wav, text) -> (B,2,T)                   ATHTDemucs_v2.py:250-326
- * The CLAP text tower (ATHTDemucs_v2.py:238-248) stays on the host side: callers pass prompt embeddings
- * (B x 512 or P x 512 fp32, L2-normalised as ClapModel.get_text_features returns them).
+ * athd_forward* take prompt embeddings (B x 512 or P x 512 fp32, L2-normalised as ClapModel.get_text_features
+ * returns them); the CLAP text tower that computes them from token ids (ATHTDemucs_v2.py:238-248) is the
+ * athd_text_* section below, with a context of its own.  Only the tokenizer stays with the caller.
  *
  * Conventions: plain pointers and sizes, no torch types.  All device pointers are HIP device memory owned by
  * the caller (wav, text embeddings, output, workspace); the context owns the packed weights.  Every call
@@ -193,6 +194,54 @@ size_t athd_eval_spectrogram_scratch_bytes(int n_signals);
 int athd_eval_spectrogram(const float* wav, int n_signals, int channels, int64_t T, int64_t signal_stride,
                           float power, int to_db, float top_db, float* out, float* range, void* scratch,
                           size_t scratch_bytes, void* stream);
+
+/* ---- CLAP text tower: token ids -> prompt embeddings (ATHTDemucs_v2.py:238-248, :282) ----
+ * RoBERTa-base (12 post-LN layers, hidden 768, 12 heads of 64, FFN 3072, exact GELU), the tanh pooler on the first
+ * token and the 768 -> 512 -> 512 ReLU projection of laion/clap-htsat-unfused, with the weights a reference checkpoint
+ * carries under clap.text_model.* / clap.text_projection.*.  A context of its own: athd_create / athd_set_weight /
+ * athd_finalize still ignore clap.* and an athd_ctx does not grow.
+ *
+ * Keys are the Hugging Face names (a leading "clap." is stripped): text_model.embeddings.{word,position,token_type}_
+ * embeddings.weight, text_model.embeddings.LayerNorm.*, text_model.encoder.layer.{0..11}.*, text_model.pooler.dense.*,
+ * text_projection.linear{1,2}.* - 203 fp32 tensors (athd_text_required_key).  Other keys (the integer buffers
+ * position_ids / token_type_ids, the audio tower) are accepted and ignored.  The dimensions are the checkpoint's and
+ * fixed: vocab 50265, 514 positions, 768 / 12 / 3072, projection 512, LayerNorm eps 1e-12, pad id 1;
+ * athd_text_finalize returns ATHD_EKEY for a missing or mis-shaped key.  dtype: ATHD_F32 = fp32 weights and fp32 MFMA;
+ * ATHD_BF16 = bf16 matrix weights and bf16-rounded GEMM inputs with fp32 accumulation (the embedding tables, biases,
+ * LayerNorms, attention scores and softmax stay fp32).
+ *
+ * Semantics, per prompt p of input_ids / attention_mask (P, L) int32:
+ *   pos = cumsum(ids != 1) * (ids != 1) + 1           (RoBERTa's rule: it reads the ids, not the mask)
+ *   x = LN(word[id] + type[0] + position[pos])
+ *   per layer: q, k, v = linear(x); scores = q k^T / 8 per head, softmax over the keys with mask != 0 (a key with mask 0
+ *     gets probability exactly 0); x = LN(out(attn) + x); x = LN(W2 gelu_erf(W1 x + b1) + b2 + x)
+ *   pooled = tanh(dense(x[:, 0])); emb = linear2(relu(linear1(pooled)))
+ *   normalize != 0: out = emb / max(||emb||2, 1e-12)   == ClapModel.get_text_features (:241-244)
+ *   normalize == 0: out = emb                          == ClapTextModelWithProjection.forward(...).text_embeds (:245-248)
+ *
+ * input_ids, attention_mask, out (P, 512) f32 and workspace are device memory (out and workspace 16-byte aligned).
+ * athd_text_encode is stream-only: no host synchronisation, no allocation and no launch-configuration query (all of
+ * that happens in athd_text_finalize), so it can be captured in a graph from the first call and `out` can be handed to
+ * athd_forward_prompts as text_table on the same stream.  ATHD_EINVAL: P outside 1..256, L outside 1..128 (one head's
+ * q, k and v sit in LDS in fp32), a null pointer; ATHD_EWORKSPACE: workspace smaller than athd_text_workspace_bytes
+ * (which is 0 for P / L out of range); ATHD_ESTATE: before athd_text_finalize.  Nothing is written in those cases.
+ * An id outside [0, 50265) cannot be reported without a synchronisation: it is clamped into the table, that prompt's
+ * row is unspecified, nothing faults and the other rows are unaffected; the same holds for a prompt whose mask is all
+ * zero.  A prompt's row depends neither on the other prompts of the call, nor on how far the batch is padded, nor on
+ * the run: masked keys contribute exact zeros, every reduction (split-K included) has a fixed order that depends on
+ * the GEMM's (N, K) only, and there are no floating-point atomics. */
+typedef struct athd_text_ctx athd_text_ctx;
+int athd_text_create(athd_text_ctx** out, int device, int dtype);
+int athd_text_set_weight(athd_text_ctx* ctx, const char* key, const void* host, const int64_t* shape, int ndim,
+                         int src_dtype);
+int athd_text_num_required_keys(void);
+const char* athd_text_required_key(int i);
+int athd_text_finalize(athd_text_ctx* ctx);
+size_t athd_text_workspace_bytes(athd_text_ctx* ctx, int P, int L);
+int athd_text_encode(athd_text_ctx* ctx, const int32_t* input_ids, const int32_t* attention_mask, int P, int L,
+                     int normalize, float* out, void* workspace, size_t workspace_bytes, void* stream);
+const char* athd_text_last_error(athd_text_ctx* ctx);
+void athd_text_destroy(athd_text_ctx* ctx);
 
 /* Kernel timing (measurement aid for bench.py; not part of the reference interface).  Between
  * athd_profile_start and athd_profile_stop every launch of kernel `kernel` (its rocprofv3 symbol without
