@@ -152,10 +152,7 @@ void encode(Run& r, const Dims& d, const Bufs& b, const float* wav) {
     KSection sec_enc("encoder");
     const int64_t B = d.B, Ts = d.Tspec;
     // ---- STFT + CaC, input normalisation statistics (ATHTDemucs_v2.py:261-275) ----
-    const int64_t pl = 1536, pr = 1536 + Ts * 1024 - d.T, maxpad = std::max(pl, pr);
-    const int64_t extra = d.T <= maxpad ? maxpad - d.T + 1 : 0, epr = std::min(pr, extra), epl = extra - epr;
-    PadPlan pp;
-    pp.L = d.T; pp.left = pl - epl; pp.ext_left = epl; pp.Lx = d.T + epl + epr;
+    const PadPlan pp = stft_pad_plan(d.T, Ts);
     double *st_spec = r.stats(B), *st_wav = r.stats(B);
     stft_launch(wav, (int)B, d.T, pp, (int)Ts, c->tw, r.actbf ? nullptr : c->tw64, c->win, b.specT, st_spec, r.s);
     stats_launch(wav, (int)B, 2 * d.T, st_wav, r.s);

@@ -14,6 +14,15 @@ struct PadPlan {
     int64_t ext_left;   // zero extension on the left (only when L <= max pad)
     int64_t Lx;         // zero-extended length
 };
+// the plan of HTDemucs._spec for T samples and Tspec = ceil(T / 1024) kept frames: pad1d(x, (1536, 1536 + 1024 Tspec - T),
+// reflect), whose zero extension (inputs no longer than the larger pad) goes to the right first, then to the left
+inline PadPlan stft_pad_plan(int64_t T, int64_t Tspec) {
+    const int64_t pl = 1536, pr = 1536 + Tspec * 1024 - T, maxpad = pl > pr ? pl : pr;
+    const int64_t extra = T <= maxpad ? maxpad - T + 1 : 0, epr = pr < extra ? pr : extra, epl = extra - epr;
+    PadPlan pp;
+    pp.L = T; pp.left = pl - epl; pp.ext_left = epl; pp.Lx = T + epl + epr;
+    return pp;
+}
 
 // tconv0.hip: time encoder level-0 conv + GELU on the raw waveform, normalisation on load; w = [48][tap*2 + c] f32
 void tconv0_launch(const float* wav, int nb, int64_t T, int64_t Lo, const float* w, const float* bias,
@@ -31,6 +40,7 @@ void istft_ola_launch(const float* fo, int NI, int Tspec, int P, int64_t T, cons
                       const double2* tw64, const float* win, const float* win2, const float* xt2, const float* tnorm,
                       float* out, float* part, hipStream_t s);
 int istft_ola_nwg(int Tspec);
+int istft_ola_frames(int Tspec);     // frames per workgroup (the last workgroup takes the rest)
 inline int64_t istft_ola_part_floats(int64_t NI, int Tspec) { return NI * istft_ola_nwg(Tspec) * 2 * 3 * 1024 * 2; }
 
 // norm.hip

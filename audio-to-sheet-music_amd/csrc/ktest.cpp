@@ -384,4 +384,62 @@ int kt_tt_attn(const KtTtAttn* d, void* stream) {
                           (int)d->L, (float*)d->out, (hipStream_t)stream);
 }
 
+// ---- the spectral front and back end, the time encoder's first conv, the prompt vectors, the position tables ----
+struct KtStft {
+    void* wav; int64_t nb, T, Tspec; void* tw; void* tw64; void* win; void* specT; void* stats;
+    int64_t pp_L, pp_left, pp_ext_left, pp_Lx;       // the explicit PadPlan (kt_stft_pad_plan gives the product's)
+};
+struct KtIstft {
+    void* fo; int64_t NI, Tspec, P, T; void* spec; void* tw; void* tw64; void* win; void* win2; void* xt2; void* tnorm;
+    void* out; void* part;
+};
+struct KtTconv0 { void* wav; int64_t nb, T, Lo; void* w; void* bias; void* tnorm; void* out; int64_t out_bf16; };
+struct KtTextVec {
+    void* text; int64_t NI, P, per_item; void* maT; void* ma; void* mcT; void* mc; void* b2; void* a; void* c0; void* c2;
+};
+int64_t kt_sizeof_stft() { return (int64_t)sizeof(KtStft); }
+int64_t kt_sizeof_istft() { return (int64_t)sizeof(KtIstft); }
+int64_t kt_sizeof_tconv0() { return (int64_t)sizeof(KtTconv0); }
+int64_t kt_sizeof_textvec() { return (int64_t)sizeof(KtTextVec); }
+
+int kt_stft(const KtStft* k, void* stream) {
+    PadPlan pp;
+    pp.L = k->pp_L; pp.left = k->pp_left; pp.ext_left = k->pp_ext_left; pp.Lx = k->pp_Lx;
+    stft_launch((const float*)k->wav, (int)k->nb, k->T, pp, (int)k->Tspec, (const float2*)k->tw, (const double2*)k->tw64,
+                (const float*)k->win, (float*)k->specT, (double*)k->stats, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+void kt_stft_pad_plan(int64_t T, int64_t Tspec, int64_t* out4) {
+    const PadPlan pp = stft_pad_plan(T, Tspec);
+    out4[0] = pp.L; out4[1] = pp.left; out4[2] = pp.ext_left; out4[3] = pp.Lx;
+}
+int kt_istft_ola(const KtIstft* k, void* stream) {
+    istft_ola_launch((const float*)k->fo, (int)k->NI, (int)k->Tspec, (int)k->P, k->T, (const float*)k->spec,
+                     (const float2*)k->tw, (const double2*)k->tw64, (const float*)k->win, (const float*)k->win2,
+                     (const float*)k->xt2, (const float*)k->tnorm, (float*)k->out, (float*)k->part, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+int64_t kt_istft_nwg(int64_t Tspec) { return istft_ola_nwg((int)Tspec); }
+int64_t kt_istft_frames(int64_t Tspec) { return istft_ola_frames((int)Tspec); }
+int64_t kt_istft_part_floats(int64_t NI, int64_t Tspec) { return istft_ola_part_floats(NI, (int)Tspec); }
+int kt_tconv0(const KtTconv0* k, void* stream) {
+    tconv0_launch((const float*)k->wav, (int)k->nb, k->T, k->Lo, (const float*)k->w, (const float*)k->bias,
+                  (const float*)k->tnorm, k->out, (int)k->out_bf16, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+int kt_text_vec(const KtTextVec* k, void* stream) {
+    text_vec_launch((const float*)k->text, (int)k->NI, (int)k->P, (int)k->per_item, (const float*)k->maT,
+                    (const float*)k->ma, (const float*)k->mcT, (const float*)k->mc, (const float*)k->b2, (float*)k->a,
+                    (float*)k->c0, (float*)k->c2, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+int kt_pos2d(float* out, int64_t Fr, int64_t T1, int64_t C, void* stream) {
+    pos2d_launch(out, (int)Fr, (int)T1, (int)C, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+int kt_pos1d(float* out, int64_t T2, int64_t C, void* stream) {
+    pos1d_launch(out, (int)T2, (int)C, (hipStream_t)stream);
+    return (int)hipGetLastError();
+}
+
 }  // extern "C"

@@ -1,7 +1,8 @@
 """ctypes binding of libathd_ktest.so (csrc/ktest.cpp): the kernel launchers of libathd.so behind flat descriptors.
-A plain helper module of tests/test_gpu_kernels.py, tests/test_gpu_dconv.py and tests/test_gpu_dec.py; importing it needs
-the built libraries but no GPU (the host-side packers, folds and shape predicates it exports are compared on the CPU,
-tests/test_dconv_refs.py, tests/test_dec_refs.py)."""
+A plain helper module of tests/test_gpu_kernels.py, tests/test_gpu_dconv.py, tests/test_gpu_dec.py and
+tests/test_gpu_spectral.py; importing it needs the built libraries but no GPU (the host-side packers, folds, plans and shape
+predicates it exports are compared on the CPU, tests/test_dconv_refs.py, tests/test_dec_refs.py,
+tests/test_spectral_refs.py)."""
 import ctypes
 import json
 import os
@@ -116,6 +117,38 @@ lib.kt_fdec1_gram_floats.restype = _I
 lib.kt_fdec1_gram_floats.argtypes = [_I, _I]
 lib.kt_dec_last_fold.restype = _I
 lib.kt_dec_last_fold.argtypes = [_P, _P, _P, _P, _I, _P]
+# ---- the spectral front and back end, tconv0, text_vec, the position tables (tests/test_gpu_spectral.py) ----
+ST_FIELDS = "wav nb T Tspec tw tw64 win specT stats pp_L pp_left pp_ext_left pp_Lx".split()
+IS_FIELDS = "fo NI Tspec P T spec tw tw64 win win2 xt2 tnorm out part".split()
+TC_FIELDS = "wav nb T Lo w bias tnorm out out_bf16".split()
+TV_FIELDS = "text NI P per_item maT ma mcT mc b2 a c0 c2".split()
+KtStft = _struct("KtStft", ST_FIELDS, set("wav tw tw64 win specT stats".split()))
+KtIstft = _struct("KtIstft", IS_FIELDS, set("fo spec tw tw64 win win2 xt2 tnorm out part".split()))
+KtTconv0 = _struct("KtTconv0", TC_FIELDS, set("wav w bias tnorm out".split()))
+KtTextVec = _struct("KtTextVec", TV_FIELDS, set("text maT ma mcT mc b2 a c0 c2".split()))
+_SPEC = (("stft", KtStft), ("istft", KtIstft), ("tconv0", KtTconv0), ("textvec", KtTextVec))
+for _n, _ in _SPEC:
+    getattr(lib, "kt_sizeof_" + _n).restype = _I
+for _n in ("stft", "istft_ola", "tconv0", "text_vec"):
+    getattr(lib, "kt_" + _n).argtypes = [_P, _P]
+lib.kt_stft_pad_plan.restype = None
+lib.kt_stft_pad_plan.argtypes = [_I, _I, _P]
+for _n in ("istft_nwg", "istft_frames"):
+    getattr(lib, "kt_" + _n).restype = _I
+    getattr(lib, "kt_" + _n).argtypes = [_I]
+lib.kt_istft_part_floats.restype = _I
+lib.kt_istft_part_floats.argtypes = [_I, _I]
+lib.kt_pos2d.argtypes = [_P, _I, _I, _I, _P]
+lib.kt_pos1d.argtypes = [_P, _I, _I, _P]
+
+
+def stft_pad_plan(T, Tspec):
+    """kernels.h stft_pad_plan -> (L, left, ext_left, Lx)"""
+    out = (ctypes.c_int64 * 4)()
+    lib.kt_stft_pad_plan(T, Tspec, out)
+    return tuple(out)
+
+
 # one LrStep of kernels.h (fdec_lr_steps_launch writes Hd + 1 of them)
 LRSTEP = np.dtype([("lz", "<f4"), ("lk", "<f4"), ("lj", "<f4"), ("zk", "<u4"), ("jj", "<u4"), ("flags", "<u4"),
                    ("pad", "<u4", (2,))])
@@ -154,7 +187,7 @@ def dconv_plan(mode, C, nb, L, rewrite_fusable):
 
 def sizes_match():
     return {n: (getattr(lib, "kt_sizeof_" + n)(), ctypes.sizeof(s))
-            for n, s in (("gemm", KtGemm), ("attn", KtAttn), ("ln", KtLn), ("convt4", KtConvT4)) + _NEW + _DEC}
+            for n, s in (("gemm", KtGemm), ("attn", KtAttn), ("ln", KtLn), ("convt4", KtConvT4)) + _NEW + _DEC + _SPEC}
 
 
 GEMM_DEFAULTS = dict(nb=1, H_in=1, W=1, a_cs=1, a_bs=-1, a_hs=-1, ntaps=1, in_stride=1, dil=1, H_out=1, H_out_total=1,
@@ -234,6 +267,7 @@ REPORT = os.path.join(os.environ.get("ATHD_OUT") or os.path.join(os.path.dirname
                                                                  "bench_out"), "kernel_parity_report.json")
 DCONV_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_dconv_report.json")
 DEC_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_dec_report.json")
+SPECTRAL_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_spectral_report.json")
 _reports = {}
 
 
