@@ -48,6 +48,13 @@ lib.athd_sdr.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_
 lib.athd_sdr.restype = _c.c_int
 lib.athd_sisdr.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p]
 lib.athd_sisdr.restype = _c.c_int
+lib.athd_loss_rows_scratch_bytes.argtypes = [_c.c_int64, _c.c_int64]
+lib.athd_loss_rows_scratch_bytes.restype = _c.c_size_t
+lib.athd_loss_rows.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p]
+lib.athd_loss_rows.restype = _c.c_int
+lib.athd_gather_segments.argtypes = [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int64,
+                                     _c.c_int64, _c.c_void_p, _c.c_void_p]
+lib.athd_gather_segments.restype = _c.c_int
 lib.athd_resample_length.argtypes = [_c.c_int64, _c.c_int, _c.c_int]
 lib.athd_resample_length.restype = _c.c_int64
 lib.athd_resample_scratch_bytes.argtypes = [_c.c_int, _c.c_int]
@@ -101,7 +108,8 @@ lib.athd_destroy.restype = None
 EXPORTED = ["athd_version", "athd_create", "athd_set_weight", "athd_num_required_keys", "athd_required_key",
             "athd_finalize", "athd_set_decode_items", "athd_workspace_bytes", "athd_forward", "athd_forward_prompts",
             "athd_num_windows", "athd_overlap_add", "athd_overlap_add_weighted", "athd_ola_normalize", "athd_sdr",
-            "athd_sisdr", "athd_resample_length", "athd_resample_scratch_bytes", "athd_resample",
+            "athd_sisdr", "athd_loss_rows_scratch_bytes", "athd_loss_rows", "athd_gather_segments",
+            "athd_resample_length", "athd_resample_scratch_bytes", "athd_resample",
             "athd_spectrogram_frames", "athd_spectrogram_db", "athd_eval_spectrogram_scratch_bytes",
             "athd_eval_spectrogram", "athd_profile_start", "athd_profile_stop", "athd_profile_count", "athd_profile_get", "athd_last_error", "athd_destroy",
             "athd_text_create", "athd_text_set_weight", "athd_text_num_required_keys", "athd_text_required_key",

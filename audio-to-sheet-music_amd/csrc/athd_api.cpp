@@ -140,7 +140,7 @@ const std::vector<std::pair<std::string, std::vector<int64_t>>>& keys() {
 // =============================================================================================== ABI
 extern "C" {
 
-int athd_version(void) { return 103; }
+int athd_version(void) { return 104; }
 
 int athd_num_required_keys(void) { return (int)keys().size(); }
 
@@ -520,6 +520,20 @@ int athd_sdr(const float* est, const float* target, int64_t rows, int64_t n, dou
 int athd_sisdr(const float* est, const float* target, int64_t rows, int64_t n, double* scratch, float* out,
                void* stream) {
     const int rc = sisdr_launch(est, target, rows, n, scratch, out, (hipStream_t)stream);
+    return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : ATHD_EHIP);
+}
+
+size_t athd_loss_rows_scratch_bytes(int64_t rows, int64_t n) { return loss_rows_scratch_bytes(rows, n); }
+
+int athd_loss_rows(const float* est, const float* target, int64_t rows, int64_t n, void* scratch, double* out,
+                   void* stream) {
+    const int rc = loss_rows_launch(est, target, rows, n, scratch, out, (hipStream_t)stream);
+    return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : ATHD_EHIP);
+}
+
+int athd_gather_segments(const float* stems, int n_src, int64_t length, const int32_t* src, const int64_t* seg,
+                         int64_t rows, int64_t seg_samples, float* out, void* stream) {
+    const int rc = gather_segments_launch(stems, n_src, length, src, seg, rows, seg_samples, out, (hipStream_t)stream);
     return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : ATHD_EHIP);
 }
 

@@ -262,6 +262,14 @@ int sdr_launch(const float* est, const float* tgt, int64_t rows, int64_t n, doub
 int sisdr_launch(const float* est, const float* tgt, int64_t rows, int64_t n, double* scratch, float* out,
                  hipStream_t s);
 
+// loss.hip: the row metrics of src/loss.py ({sdr, sisdr, new_sdr, l1} per row, fixed-order fp64 sums, no atomics) and
+// the dataset segments of src/dataloader.py:104-121; -1 = bad argument, otherwise a HIP error
+size_t loss_rows_scratch_bytes(int64_t rows, int64_t n);
+int loss_rows_launch(const float* est, const float* tgt, int64_t rows, int64_t n, void* scratch, double* out,
+                     hipStream_t s);
+int gather_segments_launch(const float* stems, int n_src, int64_t length, const int32_t* src, const int64_t* seg,
+                           int64_t rows, int64_t seg_samples, float* out, hipStream_t s);
+
 // audio_io.hip: torchaudio-default resampler (band-table form) and the dB spectrogram of app.py:74-94.
 // resample_launch returns -1 (bad argument / unsupported pair), -5 (scratch too small) or a HIP error
 int64_t resample_length(int64_t length, int orig, int nw);

@@ -124,6 +124,36 @@ int athd_sdr(const float* est, const float* target, int64_t rows, int64_t n, dou
 int athd_sisdr(const float* est, const float* target, int64_t rows, int64_t n, double* scratch, float* out,
                void* stream);
 
+/* ---- Validation level: the metrics of src/loss.py per row and the dataset segments of src/dataloader.py, as
+ * validate() of src/train.py:132-202 consumes them ----
+ * Stream-only like the track level: no context, no allocation, no host synchronisation, work enqueued on `stream`,
+ * capturable in a graph on one stream.
+ *
+ * Row metrics of src/loss.py in one call.  est/target: device (rows, n) f32, rows contiguous.
+ * out: device (rows, 4) f64 = { sdr, sisdr, new_sdr, l1 } per row:
+ *   sdr     = clamp(10 log10((sum t^2 + 1e-8) / (sum (t-e)^2 + 1e-8)), -30, 30)          loss.py:9-30, one row
+ *   sisdr   = loss.py:33-68 for one row (zero-mean e and t, delta placement as written), clamped to +-30
+ *   new_sdr = the same ratio as sdr, not clamped                                       loss.py:71-87
+ *   l1      = mean |e - t| over the row                                                loss.py:150, one row
+ * All sums in fp64, two sweeps over the data (the second centres on the means of the first).  Every block writes its
+ * partial sums to `scratch` and a row's partials are added in a fixed order (no floating-point atomics): the table is
+ * the same bits on every run.  Loads are 16 bytes wide from the first 16-byte boundary of each est row when the target
+ * row is aligned at the same element (scalar loads otherwise).  scratch: device, 8-byte aligned,
+ * athd_loss_rows_scratch_bytes() bytes, not initialised by the caller.  1 <= rows <= 2^20, 1 <= n < 2^31; outside that
+ * athd_loss_rows_scratch_bytes returns 0 and athd_loss_rows ATHD_EINVAL. */
+size_t athd_loss_rows_scratch_bytes(int64_t rows, int64_t n);
+int athd_loss_rows(const float* est, const float* target, int64_t rows, int64_t n, void* scratch, double* out,
+                   void* stream);
+
+/* Dataset segments of src/dataloader.py:104-121 (random_segments = False) taken on the device.
+ * stems: device (n_src, length, 2) f32, frames interleaved exactly as MusDBTracks.load_stems returns them.
+ * Row r of out (rows, 2, seg_samples) = source src[r], samples [seg[r]*seg_samples, (seg[r]+1)*seg_samples),
+ * channel-major, zero beyond `length`.  src: device int32 (rows), seg: device int64 (rows).  One launch; a row whose
+ * src is outside [0, n_src) or whose seg is negative cannot be reported without a synchronisation: it is all zeros and
+ * nothing outside `stems` is read. */
+int athd_gather_segments(const float* stems, int n_src, int64_t length, const int32_t* src, const int64_t* seg,
+                         int64_t rows, int64_t seg_samples, float* out, void* stream);
+
 /* ---- Audio front end: the user path of app.py:74-126 (a file of any rate, mono or stereo) ----
  * Stream-only like the track level: no context, no host synchronisation, no device allocation, work enqueued on
  * `stream`.
