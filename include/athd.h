@@ -105,8 +105,9 @@ int athd_overlap_add(const float* windows, int64_t length, int64_t chunk_len, in
  * windows: device (k1-k0, n_stems, 2, chunk_len) f32.  weight == NULL: out (n_stems, 2, span) = the normalised
  * track span of windows [k0, k1) (the track itself for the full range).  weight != NULL (device, span floats):
  * out = the unnormalised sum and weight = the weight sum of the span, for sharded runs that add spans of window
- * ranges (the sum over ranks in rank order equals the single-range sum bit for bit) and then normalise with
- * athd_ola_normalize. */
+ * ranges and then normalise with athd_ola_normalize.  With overlap <= hop (at most one window of a later range on
+ * any sample) the sum over ranks in rank order equals the single-range sum bit for bit; with hop < overlap a later
+ * range adds its own terms first, so the sums can differ in the last bits (float addition does not re-associate). */
 int athd_overlap_add_weighted(const float* windows, int64_t length, int64_t chunk_len, int64_t overlap, int n_stems,
                               int64_t k0, int64_t k1, float* out, float* weight, void* stream);
 /* out (rows, n) /= max(weight (n), 1e-8) in place (benchmark.py:201-202). */
@@ -114,13 +115,15 @@ int athd_ola_normalize(float* out, const float* weight, int rows, int64_t n, voi
 
 /* SDR of src/loss.py:9-30 with the sign of test_inference.py:153: est/target device (rows, n) f32 ->
  * *out (device f32) = mean over rows of clamp(10 log10((sum t^2 + 1e-8) / (sum (t-e)^2 + 1e-8)), -30, 30).
- * scratch: device, 2*rows doubles.  Sums are accumulated in fp64. */
+ * scratch: device, 2*rows doubles.  Sums are accumulated in fp64.  1 <= rows <= 65535 and n >= 1; anything else
+ * returns ATHD_EINVAL and writes nothing (neither *out nor scratch). */
 int athd_sdr(const float* est, const float* target, int64_t rows, int64_t n, double* scratch, float* out,
              void* stream);
 
 /* SI-SDR of src/loss.py:33-68 with the sign of benchmark.py:586: per row, zero-mean est e and target t,
  * a = <e,t> / (|t|^2 + 1e-8), clamp(10 log10((|a t|^2 + 1e-8) / (|e - a t|^2 + 1e-8)), -30, 30), mean over
- * rows -> *out (device f32).  scratch: device, 5*rows doubles.  fp64 sums. */
+ * rows -> *out (device f32).  scratch: device, 5*rows doubles.  fp64 sums.  1 <= rows <= 65535 and n >= 1, as
+ * for athd_sdr. */
 int athd_sisdr(const float* est, const float* target, int64_t rows, int64_t n, double* scratch, float* out,
                void* stream);
 

@@ -1,6 +1,6 @@
 """ctypes binding of libathd_ktest.so (csrc/ktest.cpp): the kernel launchers of libathd.so behind flat descriptors.
 A plain helper module of tests/test_gpu_kernels.py, tests/test_gpu_dconv.py, tests/test_gpu_dec.py and
-tests/test_gpu_spectral.py; importing it needs the built libraries but no GPU (the host-side packers, folds, plans and shape
+tests/test_gpu_spectral.py (tests/test_gpu_track_kernels.py uses its buffers, sync and report only); importing it needs the built libraries but no GPU (the host-side packers, folds, plans and shape
 predicates it exports are compared on the CPU, tests/test_dconv_refs.py, tests/test_dec_refs.py,
 tests/test_spectral_refs.py)."""
 import ctypes
@@ -268,6 +268,7 @@ REPORT = os.path.join(os.environ.get("ATHD_OUT") or os.path.join(os.path.dirname
 DCONV_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_dconv_report.json")
 DEC_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_dec_report.json")
 SPECTRAL_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_spectral_report.json")
+TRACK_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_track_report.json")
 _reports = {}
 
 
