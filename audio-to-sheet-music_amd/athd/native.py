@@ -71,6 +71,11 @@ lib.athd_eval_spectrogram_scratch_bytes.restype = _c.c_size_t
 lib.athd_eval_spectrogram.argtypes = [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_float, _c.c_int,
                                       _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]
 lib.athd_eval_spectrogram.restype = _c.c_int
+lib.athd_embed_compare_scratch_bytes.argtypes = [_c.c_int, _c.c_int]
+lib.athd_embed_compare_scratch_bytes.restype = _c.c_size_t
+lib.athd_embed_compare.argtypes = [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                   _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]
+lib.athd_embed_compare.restype = _c.c_int
 lib.athd_set_decode_items.argtypes = [_c.c_void_p, _c.c_int64]
 lib.athd_set_decode_items.restype = _c.c_int
 lib.athd_profile_start.argtypes = [_c.c_void_p, _c.c_char_p]
@@ -114,7 +119,7 @@ EXPORTED = ["athd_version", "athd_create", "athd_set_weight", "athd_num_required
             "athd_eval_spectrogram", "athd_profile_start", "athd_profile_stop", "athd_profile_count", "athd_profile_get", "athd_last_error", "athd_destroy",
             "athd_text_create", "athd_text_set_weight", "athd_text_num_required_keys", "athd_text_required_key",
             "athd_text_finalize", "athd_text_workspace_bytes", "athd_text_encode", "athd_text_last_error",
-            "athd_text_destroy"]
+            "athd_text_destroy", "athd_embed_compare_scratch_bytes", "athd_embed_compare"]
 
 F32, BF16 = 0, 1
 

@@ -568,6 +568,15 @@ int athd_eval_spectrogram(const float* wav, int n_signals, int channels, int64_t
     return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : (rc == -5 ? ATHD_EWORKSPACE : ATHD_EHIP));
 }
 
+size_t athd_embed_compare_scratch_bytes(int n, int d) { return embed_compare_scratch_bytes(n, d); }
+
+int athd_embed_compare(const float* emb, int n, int d, int64_t row_stride, const int32_t* category, float* normed,
+                       float* sim, float* dist, double* stats, void* scratch, size_t scratch_bytes, void* stream) {
+    const int rc = embed_compare_launch(emb, n, d, row_stride, category, normed, sim, dist, stats, scratch,
+                                        scratch_bytes, (hipStream_t)stream);
+    return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : (rc == -5 ? ATHD_EWORKSPACE : ATHD_EHIP));
+}
+
 int athd_profile_start(athd_ctx* c, const char* kernel) {
     if (!c) return ATHD_EINVAL;
     delete c->prof;

@@ -285,4 +285,11 @@ int eval_spectrogram_launch(const float* wav, int n_signals, int channels, int64
                             float power, int to_db, float top_db, float* out, float* range, void* scratch,
                             size_t scratch_bytes, hipStream_t s);
 
+// embed_compare.hip: row normalisation, cosine-similarity and Euclidean-distance matrices and the intra / inter
+// category statistics of embedding_comparison.py (fp64 accumulation, fixed-order reductions, no atomics);
+// embed_compare_launch returns -1 (bad argument), -5 (scratch too small) or a HIP error
+size_t embed_compare_scratch_bytes(int n, int d);
+int embed_compare_launch(const float* emb, int n, int d, int64_t row_stride, const int32_t* category, float* normed,
+                         float* sim, float* dist, double* stats, void* scratch, size_t scratch_bytes, hipStream_t s);
+
 }  // namespace athd

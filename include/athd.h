@@ -228,6 +228,38 @@ int athd_eval_spectrogram(const float* wav, int n_signals, int channels, int64_t
                           float power, int to_db, float top_db, float* out, float* range, void* scratch,
                           size_t scratch_bytes, void* stream);
 
+/* ---- Embedding comparison: embedding_comparison.py:109-111 (row normalisation), :177-184 (scikit-learn's
+ * cosine_similarity and euclidean_distances) and :307-333 (analyze_clustering), for a table of n embeddings ----
+ * Stream-only like the track and validation levels: no context, no allocation, no host synchronisation, three launches
+ * on `stream` (rows, upper-triangular 64 x 64 tiles, one reduction), capturable in a graph on one stream.
+ *
+ * emb: device f32, n rows of d values, row_stride >= d elements apart.  category: device (n) int32, any values; NULL
+ * only if stats is NULL.  Outputs, each NULL = skip it: normed (n, d) f32, sim (n, n) f32, dist (n, n) f32, stats 8
+ * doubles.
+ *   normed[i] = emb[i] / (||emb[i]|| + 1e-8): the sum of squares in fp64, the norm rounded to f32, the addition and the
+ *               division in f32 (numpy's float32 arithmetic); a zero row stays zero.
+ *   g_ij      = <normed_i, normed_j>, the f32 rows accumulated in fp64.
+ *   sim[i,j]  = g_ij / (sqrt(g_ii) sqrt(g_jj)), a zero norm replaced by 1 (scikit-learn's normalize): a zero row gives
+ *               a zero row and column, its diagonal entry included.  Rounded once to f32.
+ *   dist[i,j] = sqrt(max(g_ii + g_jj - 2 g_ij, 0)) in fp64, rounded once to f32; the diagonal is exactly 0.
+ *   Each pair i <= j is computed once and stored at [i,j] and [j,i]: both matrices are bit-symmetric.  g_ii, g_jj and
+ *   g_ij are summed in the same order, so two rows of identical bits have distance exactly 0.
+ *   stats     = { intra_mean, intra_std, inter_mean, inter_std, separation, n_intra, n_inter, 0 } over the pairs i < j
+ *               of the f32 values written (or that would be written) to sim, split by category[i] == category[j], in
+ *               fp64; std is the population standard deviation, centred (exactly 0 for constant data); an empty class
+ *               gives NaN for its mean and std and for the separation (np.mean([]) in the reference).
+ * Every tile writes its partial counts and sums to `scratch` and the last launch adds them in a fixed order (no
+ * floating-point atomics): all outputs are the same bits on every run and under graph replay.  Loads are 16 bytes wide
+ * where a row's groups of four start on a 16-byte boundary, scalar otherwise (any 4-byte aligned emb and row_stride).
+ *
+ * scratch: device, 8-byte aligned, athd_embed_compare_scratch_bytes() bytes, not initialised by the caller.
+ * 1 <= n <= 4096, 1 <= d <= 4096, row_stride >= d; outside that athd_embed_compare_scratch_bytes returns 0 and
+ * athd_embed_compare ATHD_EINVAL, as for a NULL emb or scratch and a NULL category with stats set.  ATHD_EWORKSPACE:
+ * scratch too small.  Nothing is written in any of these cases. */
+size_t athd_embed_compare_scratch_bytes(int n, int d);
+int athd_embed_compare(const float* emb, int n, int d, int64_t row_stride, const int32_t* category, float* normed,
+                       float* sim, float* dist, double* stats, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- CLAP text tower: token ids -> prompt embeddings (ATHTDemucs_v2.py:238-248, :282) ----
  * RoBERTa-base (12 post-LN layers, hidden 768, 12 heads of 64, FFN 3072, exact GELU), the tanh pooler on the first
  * token and the 768 -> 512 -> 512 ReLU projection of laion/clap-htsat-unfused, with the weights a reference checkpoint
