@@ -55,6 +55,17 @@ lib.athd_loss_rows.restype = _c.c_int
 lib.athd_gather_segments.argtypes = [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                      _c.c_int64, _c.c_void_p, _c.c_void_p]
 lib.athd_gather_segments.restype = _c.c_int
+lib.athd_loss_grad_scratch_bytes.argtypes = [_c.c_int64, _c.c_int64]
+lib.athd_loss_grad_scratch_bytes.restype = _c.c_size_t
+lib.athd_loss_grad_coef.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                    _c.c_void_p, _c.c_void_p]
+lib.athd_loss_grad_coef.restype = _c.c_int
+lib.athd_loss_grad_apply.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_double,
+                                     _c.c_double, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p]
+lib.athd_loss_grad_apply.restype = _c.c_int
+lib.athd_gather_train_segments.argtypes = [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                           _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p]
+lib.athd_gather_train_segments.restype = _c.c_int
 lib.athd_resample_length.argtypes = [_c.c_int64, _c.c_int, _c.c_int]
 lib.athd_resample_length.restype = _c.c_int64
 lib.athd_resample_scratch_bytes.argtypes = [_c.c_int, _c.c_int]
@@ -119,7 +130,9 @@ EXPORTED = ["athd_version", "athd_create", "athd_set_weight", "athd_num_required
             "athd_eval_spectrogram", "athd_profile_start", "athd_profile_stop", "athd_profile_count", "athd_profile_get", "athd_last_error", "athd_destroy",
             "athd_text_create", "athd_text_set_weight", "athd_text_num_required_keys", "athd_text_required_key",
             "athd_text_finalize", "athd_text_workspace_bytes", "athd_text_encode", "athd_text_last_error",
-            "athd_text_destroy", "athd_embed_compare_scratch_bytes", "athd_embed_compare"]
+            "athd_text_destroy", "athd_embed_compare_scratch_bytes", "athd_embed_compare",
+            "athd_loss_grad_scratch_bytes", "athd_loss_grad_coef", "athd_loss_grad_apply",
+            "athd_gather_train_segments"]
 
 F32, BF16 = 0, 1
 

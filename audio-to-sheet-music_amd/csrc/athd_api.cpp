@@ -537,6 +537,29 @@ int athd_gather_segments(const float* stems, int n_src, int64_t length, const in
     return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : ATHD_EHIP);
 }
 
+size_t athd_loss_grad_scratch_bytes(int64_t rows, int64_t n) { return loss_rows_scratch_bytes(rows, n); }
+
+int athd_loss_grad_coef(const float* est, const float* target, int64_t rows, int64_t n, void* scratch, double* table,
+                        double* coef, void* stream) {
+    const int rc = loss_grad_coef_launch(est, target, rows, n, scratch, table, coef, (hipStream_t)stream);
+    return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : ATHD_EHIP);
+}
+
+int athd_loss_grad_apply(const float* est, const float* target, int64_t rows, int64_t n, const double* coef,
+                         double w_sdr, double w_sisdr, double w_l1, const float* upstream, float* grad, void* stream) {
+    const int rc = loss_grad_apply_launch(est, target, rows, n, coef, w_sdr, w_sisdr, w_l1, upstream, grad,
+                                          (hipStream_t)stream);
+    return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : ATHD_EHIP);
+}
+
+int athd_gather_train_segments(const float* stems, int n_src, int64_t length, const int32_t* src, const int64_t* start,
+                               const double* gain, const uint8_t* swap, int64_t rows, int64_t seg_samples, float* out,
+                               void* stream) {
+    const int rc = gather_train_segments_launch(stems, n_src, length, src, start, gain, swap, rows, seg_samples, out,
+                                                (hipStream_t)stream);
+    return rc == 0 ? ATHD_OK : (rc == -1 ? ATHD_EINVAL : ATHD_EHIP);
+}
+
 int64_t athd_resample_length(int64_t length, int orig_freq, int new_freq) {
     return resample_length(length, orig_freq, new_freq);
 }

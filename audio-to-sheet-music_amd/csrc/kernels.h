@@ -269,6 +269,15 @@ int loss_rows_launch(const float* est, const float* tgt, int64_t rows, int64_t n
                      hipStream_t s);
 int gather_segments_launch(const float* stems, int n_src, int64_t length, const int32_t* src, const int64_t* seg,
                            int64_t rows, int64_t seg_samples, float* out, hipStream_t s);
+// loss.hip, training ends: the gradient of the combined losses w.r.t. est (per-row coefficients from the sums of
+// loss_rows, then one elementwise pass) and the random / augmented segments of src/dataloader.py:86-134
+int loss_grad_coef_launch(const float* est, const float* tgt, int64_t rows, int64_t n, void* scratch, double* table,
+                          double* coef, hipStream_t s);
+int loss_grad_apply_launch(const float* est, const float* tgt, int64_t rows, int64_t n, const double* coef,
+                           double w_sdr, double w_si, double w_l1, const float* upstream, float* grad, hipStream_t s);
+int gather_train_segments_launch(const float* stems, int n_src, int64_t length, const int32_t* src,
+                                 const int64_t* start, const double* gain, const uint8_t* swap, int64_t rows,
+                                 int64_t seg_samples, float* out, hipStream_t s);
 
 // audio_io.hip: torchaudio-default resampler (band-table form) and the dB spectrogram of app.py:74-94.
 // resample_launch returns -1 (bad argument / unsupported pair), -5 (scratch too small) or a HIP error

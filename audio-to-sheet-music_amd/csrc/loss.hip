@@ -1,6 +1,8 @@
 // Validation level: the row metrics of src/loss.py (sdr_loss :9-30, sisdr_loss :33-68, new_sdr_metric :71-87, the L1 of
 // combined_L1_sdr_loss :150) for every row of a batch in one call, and the dataset segments of
-// src/dataloader.py:104-121 (random_segments = False) taken on the device.
+// src/dataloader.py:104-121 (random_segments = False) taken on the device.  Training ends (further down): the gradient
+// of the two combined losses with respect to est from the same sums, and the random / augmented segments of
+// src/dataloader.py:86-134.
 //
 // loss_rows: a pure streaming reduction, 8 * rows * n bytes per sweep, two sweeps.
 //   sweep 1  sum t^2, sum (t-e)^2, sum |t-e|, sum e, sum t           -> SDR, new-SDR, L1 and the row means
@@ -195,6 +197,140 @@ int loss_rows_launch(const float* est, const float* tgt, int64_t rows, int64_t n
     return (int)hipGetLastError();
 }
 
+// ---- loss gradients: d total / d est for total = -(w_sdr mean sdr + w_si mean sisdr) + w_l1 mean |e - t| (the two
+//      combined losses of src/loss.py:90-162; the clamps pass the gradient on the closed interval, as torch.clamp).
+//      coef: the table by the four launches above (so its bits are those of loss_rows), then one thread per row turns
+//      the row's sums into GC_STRIDE doubles.  apply: grad_i = cs (e_i - t_i) + cp (e_i - me) + cq (t_i - mt) +
+//      cl sign(e_i - t_i), the four scalars from the row's coefficients, the weights, 1 / rows and the upstream
+//      gradient; fp64 per element, rounded once.  The centring adds no mean term: sum (e - me) = sum (t - mt) = 0.
+constexpr int GC_STRIDE = 8;   // { a_sdr, p, q, gate_sdr, gate_si, mean e, mean t, 0 } (include/athd.h)
+constexpr double K_DB = 4.342944819032518;   // 10 / ln 10
+
+// The SDR gate reads the unclamped column of the table.  The SI-SDR column is clamped: a value strictly inside
+// +-30 is an open gate; at exactly +-30 the unclamped value (the expressions of loss_rows_final_kernel on the same
+// sums) decides between "on the boundary" (open) and "beyond it" (closed).
+__global__ __launch_bounds__(LR_THREADS) void loss_grad_coef_kernel(const double* __restrict__ rowsum,
+                                                                    const double* __restrict__ part2,
+                                                                    const double* __restrict__ table, int64_t rows,
+                                                                    int64_t n, int nb, double* __restrict__ coef) {
+    const int64_t r = (int64_t)blockIdx.x * LR_THREADS + threadIdx.x;
+    if (r >= rows) return;
+    double et = 0.0, tt = 0.0, ee = 0.0;
+    for (int b = 0; b < nb; ++b) {
+        et += part2[(r * nb + b) * 3];
+        tt += part2[(r * nb + b) * 3 + 1];
+        ee += part2[(r * nb + b) * 3 + 2];
+    }
+    const double al = et / (tt + 1e-8);
+    const double st = al * al * tt;
+    double en = ee - 2.0 * al * et + al * al * tt;
+    en = en < 0.0 ? 0.0 : en;
+    const double raw = table[4 * r + 2], sic = table[4 * r + 1];
+    const double siu = 10.0 * log10((st + 1e-8) / (en + 1e-8));
+    const bool g1 = raw >= -30.0 && raw <= 30.0;
+    const bool g2 = fabs(sic) < 30.0 || (siu >= -30.0 && siu <= 30.0);
+    const double c = et * 1e-8 / (tt + 1e-8);
+    double* o = coef + GC_STRIDE * r;
+    o[0] = 2.0 * K_DB / (rowsum[5 * r + 1] + 1e-8);
+    o[1] = -2.0 * K_DB / (en + 1e-8);
+    o[2] = K_DB * (2.0 * al * tt / ((tt + 1e-8) * (st + 1e-8)) + 2.0 * al / (en + 1e-8) +
+                   2.0 * c / ((tt + 1e-8) * (en + 1e-8)));
+    o[3] = g1 ? 1.0 : 0.0;
+    o[4] = g2 ? 1.0 : 0.0;
+    o[5] = rowsum[5 * r + 3] / (double)n;
+    o[6] = rowsum[5 * r + 4] / (double)n;
+    o[7] = 0.0;
+}
+
+struct GradScalars {
+    double cs, cp, cq, cl, me, mt;
+    bool zero;
+};
+
+ATHD_DEV float grad_value(const GradScalars& k, float ef, float tf) {
+    if (k.zero) return 0.f;
+    const double e = ef, t = tf, d = e - t;
+    const double sg = d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
+    return (float)(k.cs * d + k.cp * (e - k.me) + k.cq * (t - k.mt) + k.cl * sg);
+}
+
+// grid: rows * nb blocks as in the sweeps; 12 bytes per element.  16-byte accesses need est, target and grad rows to
+// reach a boundary at the same element.
+__global__ __launch_bounds__(LR_THREADS) void loss_grad_apply_kernel(const float* __restrict__ est,
+                                                                     const float* __restrict__ tgt, int64_t rows,
+                                                                     int64_t n, int nb, const double* __restrict__ coef,
+                                                                     double w_sdr, double w_si, double w_l1,
+                                                                     const float* __restrict__ upstream,
+                                                                     float* __restrict__ grad) {
+    const int64_t r = (int64_t)blockIdx.x / nb;
+    const int b = (int)((int64_t)blockIdx.x % nb);
+    const float* e = est + r * n;
+    const float* t = tgt + r * n;
+    float* o = grad + r * n;
+    RowSplit sp = row_split(e, t, n);
+    sp.vec = sp.vec && (((uintptr_t)(o + sp.head)) & 15) == 0;
+    const double* c = coef + GC_STRIDE * r;
+    const double up = upstream ? (double)*upstream : 1.0;
+    const double inv_rows = 1.0 / (double)rows;
+    GradScalars k;
+    k.cs = c[3] != 0.0 ? up * w_sdr * c[0] * inv_rows : 0.0;
+    k.cp = c[4] != 0.0 ? -(up * w_si * c[1] * inv_rows) : 0.0;
+    k.cq = c[4] != 0.0 ? -(up * w_si * c[2] * inv_rows) : 0.0;
+    k.cl = up * w_l1 / ((double)rows * (double)n);
+    k.me = c[5];
+    k.mt = c[6];
+    k.zero = k.cs == 0.0 && k.cp == 0.0 && k.cq == 0.0 && k.cl == 0.0;
+    const float* eg = e + sp.head;
+    const float* tg = t + sp.head;
+    float* og = o + sp.head;
+    for (int64_t ch = b; ch * LR_GROUPS < sp.groups; ch += nb) {
+        const int64_t g1 = (ch + 1) * LR_GROUPS < sp.groups ? (ch + 1) * LR_GROUPS : sp.groups;
+#pragma unroll 4
+        for (int64_t g = ch * LR_GROUPS + threadIdx.x; g < g1; g += LR_THREADS) {
+            float ev[4], tv[4], gv[4];
+            load4(eg + 4 * g, sp.vec, ev);
+            load4(tg + 4 * g, sp.vec, tv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) gv[j] = grad_value(k, ev[j], tv[j]);
+            if (sp.vec) {
+                *reinterpret_cast<float4*>(og + 4 * g) = make_float4(gv[0], gv[1], gv[2], gv[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) og[4 * g + j] = gv[j];
+            }
+        }
+    }
+    if (b == 0) {      // the row's scalar head and tail, as in the sweeps
+        const int64_t i = threadIdx.x < sp.head ? (int64_t)threadIdx.x : sp.tail0 + ((int64_t)threadIdx.x - sp.head);
+        if (i < n) o[i] = grad_value(k, e[i], t[i]);
+    }
+}
+
+int loss_grad_coef_launch(const float* est, const float* tgt, int64_t rows, int64_t n, void* scratch, double* table,
+                          double* coef, hipStream_t s) {
+    if (!coef || ((uintptr_t)coef & 7)) return -1;
+    const int rc = loss_rows_launch(est, tgt, rows, n, scratch, table, s);
+    if (rc != 0) return rc;
+    const int nb = (int)lr_blocks_per_row(rows, n);
+    const double* rowsum = (const double*)scratch + rows * nb * 5;
+    const double* part2 = rowsum + rows * 5;
+    hipLaunchKernelGGL(loss_grad_coef_kernel, dim3((unsigned)((rows + LR_THREADS - 1) / LR_THREADS)), dim3(LR_THREADS),
+                       0, s, rowsum, part2, (const double*)table, rows, n, nb, coef);
+    return (int)hipGetLastError();
+}
+
+int loss_grad_apply_launch(const float* est, const float* tgt, int64_t rows, int64_t n, const double* coef,
+                           double w_sdr, double w_si, double w_l1, const float* upstream, float* grad, hipStream_t s) {
+    if (!est || !tgt || !coef || !grad || !loss_rows_shape_ok(rows, n)) return -1;
+    if (((uintptr_t)est & 3) || ((uintptr_t)tgt & 3) || ((uintptr_t)grad & 3) || ((uintptr_t)upstream & 3) ||
+        ((uintptr_t)coef & 7))
+        return -1;
+    const int nb = (int)lr_blocks_per_row(rows, n);
+    hipLaunchKernelGGL(loss_grad_apply_kernel, dim3((unsigned)(rows * nb)), dim3(LR_THREADS), 0, s, est, tgt, rows, n,
+                       nb, coef, w_sdr, w_si, w_l1, upstream, grad);
+    return (int)hipGetLastError();
+}
+
 // ---- dataset segments: out (rows, 2, S) channel-major from stems (n_src, length, 2) frame-interleaved.  Tile
 //      (row, x) of rows * ceil(S / 256), tiles strided over the grid: thread j reads frame seg * S + j of source src (one 8-byte load where the
 //      base allows it) and stores its two channels, each a coalesced 4-byte store.  A frame beyond `length`, a source
@@ -236,6 +372,64 @@ int gather_segments_launch(const float* stems, int n_src, int64_t length, const 
     const int64_t tiles = rows * bx;
     hipLaunchKernelGGL(gather_segments_kernel, dim3((unsigned)std::min<int64_t>(tiles, LR_MAX_GRID)), dim3(256), 0, s,
                        stems, n_src, length, src, seg, S, bx, tiles, (int)(((uintptr_t)stems & 7) == 0), out);
+    return (int)hipGetLastError();
+}
+
+// ---- training segments (src/dataloader.py:86-134 on the device): the same tiles, but row r starts at any sample
+//      start[r], every sample is (float)((double)x * gain[r]) (the reference multiplies stempeg's float64 array and
+//      rounds once with .float(): the same bits for f32-representable samples; gain 1.0 returns x) and the channels
+//      are exchanged where swap[r] is set.  A frame address is 8-byte aligned whenever the base is, whatever the
+//      start, so the load route is chosen once per launch.  A source outside [0, n_src) or a start outside
+//      [0, length] gives zeros.
+__global__ __launch_bounds__(256) void gather_train_segments_kernel(const float* __restrict__ stems, int n_src,
+                                                                    int64_t length, const int32_t* __restrict__ src,
+                                                                    const int64_t* __restrict__ start,
+                                                                    const double* __restrict__ gain,
+                                                                    const uint8_t* __restrict__ swap, int64_t S,
+                                                                    int64_t bx, int64_t tiles, int vec,
+                                                                    float* __restrict__ out) {
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t r = tile / bx;
+    const int64_t j = (tile % bx) * 256 + threadIdx.x;
+    if (j >= S) continue;
+    const int sr = src[r];
+    const int64_t st = start[r];
+    float a = 0.f, b = 0.f;
+    if (sr >= 0 && sr < n_src && st >= 0 && st < length && j < length - st) {
+        const float* p = stems + ((int64_t)sr * length + st + j) * 2;
+        float x, y;
+        if (vec) {
+            const float2 q = *reinterpret_cast<const float2*>(p);
+            x = q.x; y = q.y;
+        } else {
+            x = p[0]; y = p[1];
+        }
+        const double gn = gain[r];
+        x = (float)((double)x * gn);
+        y = (float)((double)y * gn);
+        const bool sw = swap[r] != 0;
+        a = sw ? y : x;
+        b = sw ? x : y;
+    }
+    out[(r * 2) * S + j] = a;
+    out[(r * 2 + 1) * S + j] = b;
+  }
+}
+
+int gather_train_segments_launch(const float* stems, int n_src, int64_t length, const int32_t* src,
+                                 const int64_t* start, const double* gain, const uint8_t* swap, int64_t rows, int64_t S,
+                                 float* out, hipStream_t s) {
+    if (!stems || !src || !start || !gain || !swap || !out || n_src <= 0 || length <= 0 || rows <= 0 || S <= 0)
+        return -1;
+    if (((uintptr_t)stems & 3) || ((uintptr_t)out & 3) || ((uintptr_t)src & 3) || ((uintptr_t)start & 7) ||
+        ((uintptr_t)gain & 7))
+        return -1;
+    const int64_t bx = (S + 255) / 256;
+    if (bx > INT64_MAX / rows) return -1;
+    const int64_t tiles = rows * bx;
+    hipLaunchKernelGGL(gather_train_segments_kernel, dim3((unsigned)std::min<int64_t>(tiles, LR_MAX_GRID)), dim3(256), 0,
+                       s, stems, n_src, length, src, start, gain, swap, S, bx, tiles,
+                       (int)(((uintptr_t)stems & 7) == 0), out);
     return (int)hipGetLastError();
 }
 

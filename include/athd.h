@@ -157,6 +157,49 @@ int athd_loss_rows(const float* est, const float* target, int64_t rows, int64_t 
 int athd_gather_segments(const float* stems, int n_src, int64_t length, const int32_t* src, const int64_t* seg,
                          int64_t rows, int64_t seg_samples, float* out, void* stream);
 
+/* ---- Training ends: the batches and the loss gradient of train_epoch (src/train.py:23-129) ----
+ * Stream-only like the validation level.  The model's own backward is not here.
+ *
+ * Gradient of total = -(w_sdr mean_r sdr_r + w_sisdr mean_r sisdr_r) + w_l1 mean |e - t| with respect to est, for the
+ * two combined losses of src/loss.py:90-162 (combined_loss: w_l1 = 0; combined_L1_sdr_loss: w_sisdr = 0).
+ *
+ * athd_loss_grad_coef runs the launches of athd_loss_rows (same scratch, same limits; `table` (rows, 4) f64 has the
+ * bits athd_loss_rows writes) and one more that writes coef: device (rows, 8) f64, per row
+ *   [0] a_sdr = 2k / (D + d)                                   k = 10 / ln 10, d = 1e-8, D = sum (t-e)^2
+ *   [1] p     = -2k / (E + d)                                  E = |(e-me) - a (t-mt)|^2, a = dot / (T + d)
+ *   [2] q     = k (2aT / ((T+d)(S+d)) + 2a / (E+d) + 2c / ((T+d)(E+d)))   T = |t-mt|^2, S = a^2 T, c = dot d / (T+d)
+ *   [3] gate_sdr   1 if -30 <= sdr <= 30 unclamped (read from table[.][2]), else 0
+ *   [4] gate_sisdr 1 if table[.][1] lies strictly inside +-30; where it is exactly +-30 the unclamped value, evaluated
+ *                  from the same sums by the same expressions, decides (on the boundary: 1, beyond: 0)
+ *   [5] me = mean e   [6] mt = mean t   [7] 0
+ * so the coefficients carry no weight, no 1/rows and no upstream gradient.  torch.clamp passes the gradient on the
+ * closed interval; so do the gates.
+ *
+ * athd_loss_grad_apply: one elementwise pass, 12 bytes per element, fp64 per element rounded once to f32:
+ *   grad_i = g [ w_sdr gate_sdr a_sdr (e_i - t_i) / rows - w_sisdr gate_sisdr (p (e_i - me) + q (t_i - mt)) / rows
+ *                + w_l1 sign(e_i - t_i) / (rows n) ],  sign(0) = 0,
+ * g = *upstream (a device f32 scalar read by the kernel, no host synchronisation), 1 when upstream is NULL.  16-byte
+ * accesses where est, target and grad rows reach a 16-byte boundary at the same element, 4-byte ones otherwise.  A row
+ * whose four scalars are all zero (both gates closed and w_l1 = 0, or g = 0) is written as +0.  No atomics: the same
+ * bits on every run.  Shapes outside the limits of athd_loss_rows, null or misaligned pointers: ATHD_EINVAL, nothing
+ * written. */
+size_t athd_loss_grad_scratch_bytes(int64_t rows, int64_t n);
+int athd_loss_grad_coef(const float* est, const float* target, int64_t rows, int64_t n, void* scratch, double* table,
+                        double* coef, void* stream);
+int athd_loss_grad_apply(const float* est, const float* target, int64_t rows, int64_t n, const double* coef,
+                         double w_sdr, double w_sisdr, double w_l1, const float* upstream, float* grad, void* stream);
+
+/* Training segments of src/dataloader.py:86-134 (random_segments = True, augment = True) taken on the device.  As
+ * athd_gather_segments, but row r starts at any sample start[r] (device int64), every sample is
+ * (float)((double)x * gain[r]) (gain: device f64) and the two channels are exchanged where swap[r] (device uint8) is
+ * set.  The reference multiplies the float64 array stempeg returns and then calls .float() (dataloader.py:123-134,
+ * 152-153): the fp64 product rounded once is bit-equal to it whenever the samples are f32-representable, which holds
+ * for every PCM file MusDBTracks reads; gain == 1.0 reproduces the input bits.  Frames past `length` are zero.  A row
+ * whose src is outside [0, n_src) or whose start is negative is all zeros and nothing outside `stems` is read. */
+int athd_gather_train_segments(const float* stems, int n_src, int64_t length, const int32_t* src, const int64_t* start,
+                               const double* gain, const uint8_t* swap, int64_t rows, int64_t seg_samples, float* out,
+                               void* stream);
+
 /* ---- Audio front end: the user path of app.py:74-126 (a file of any rate, mono or stereo) ----
  * Stream-only like the track level: no context, no host synchronisation, no device allocation, work enqueued on
  * `stream`.
