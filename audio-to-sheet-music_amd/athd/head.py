@@ -1,0 +1,195 @@
+"""The trainable half of the reference model as a plain torch module, fed by the native frozen half.
+
+The reference trains only `text_attn`, `freq_decoder`, `time_decoder`, `freq_out` and `time_out` (`ATHTDemucs_v2.py:170-188`);
+the HTDemucs encoders, the cross-transformer and CLAP run frozen under `no_grad` (`:277-279`).  `AudioTextHTDemucs.encode`
+(athd/model.py, `athd_encode`) computes that frozen half in libathd.so; `TrainableHead` is the rest (`:21-139, 282-324`),
+differentiable by autograd on any device and dtype; `HeadTrainer` joins the two behind the `model(mixture, prompts)`
+call that `athd.train.train_epoch` expects.  The model's backward stays torch's.
+
+`TrainableHead.state_dict()` has exactly the 50 reference key names and shapes outside `htdemucs.` / `clap.`
+(`athd.weights.hot_path_spec`), so a trained head drops into a reference-format checkpoint and loads straight back into
+the native inference path (`HeadTrainer.sync`).
+
+Dead parameters.  The text cross-attention has ONE key (the prompt embedding), so its softmax is identically 1 and the
+attention output does not depend on the query or the key.  `text_attn.q_proj.*`, `text_attn.k_proj.*`,
+`text_attn.norm_q.*` and the query and key thirds of `text_attn.attn.in_proj_*` therefore get a mathematically zero
+gradient (rounding leaves values around 1e-24 of the live gradients).  They stay parameters with `requires_grad=True`, as
+in the reference: an optimizer with weight decay moves them exactly as it does there.
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .model import EncodedFeatures
+from .weights import DEC_CH, MODEL_DIM, TEXT_DIM, hot_path_spec
+
+N_FFT, HOP = 4096, 1024
+
+
+def head_keys():
+    """[(key, shape)] of the 50 reference-owned tensors, in `hot_path_spec` order"""
+    return [(k, tuple(s)) for k, s, _ in hot_path_spec() if not k.startswith("htdemucs.")]
+
+
+class _TextAttention(nn.Module):
+    """`ATHTDemucs_v2.py:21-58`: every feature row attends to the one prompt token, then a residual MLP and a LayerNorm"""
+
+    def __init__(self, dim: int = MODEL_DIM, text_dim: int = TEXT_DIM, heads: int = 8):
+        super().__init__()
+        self.q_proj = nn.Linear(dim, dim)
+        self.k_proj = nn.Linear(text_dim, dim)
+        self.v_proj = nn.Linear(text_dim, dim)
+        self.attn = nn.MultiheadAttention(dim, heads, batch_first=True)
+        self.out_mlp = nn.Sequential(nn.Linear(dim, dim), nn.GELU(), nn.Linear(dim, dim))
+        self.norm_q = nn.LayerNorm(dim)
+        self.norm_out = nn.LayerNorm(dim)
+
+    def rows(self, seq: torch.Tensor, text: torch.Tensor) -> torch.Tensor:
+        """seq (B, N, D), text (B, 1, text_dim)"""
+        q = self.q_proj(self.norm_q(seq))
+        a, _ = self.attn(q, self.k_proj(text), self.v_proj(text), need_weights=False)
+        u = seq + a
+        return self.norm_out(u + self.out_mlp(u))
+
+    def forward(self, x: torch.Tensor, xt: torch.Tensor, text_emb: torch.Tensor):
+        text = text_emb[:, None, :] if text_emb.dim() == 2 else text_emb
+        B, C, Fr, Ts = x.shape
+        xs = self.rows(x.flatten(2).transpose(1, 2), text)            # (B, Fr * Ts, C), frequency-major as the reference
+        xts = self.rows(xt.transpose(1, 2), text)
+        return xs.transpose(1, 2).reshape(B, C, Fr, Ts), xts.transpose(1, 2)
+
+
+class _Decoder(nn.Module):
+    """`ATHTDemucs_v2.py:61-139`: four ConvTranspose (k 8, s 4, p 2) levels along the frequency axis (freq) or time (time);
+    GroupNorm(1) + GELU on all but the last; each level resized to its target length, then the encoder skip of that
+    level (its first C_out channels, resized the same way) added times 0.1."""
+
+    def __init__(self, freq: bool):
+        super().__init__()
+        self.freq = freq
+        self.layers = nn.ModuleList()
+        for i in range(len(DEC_CH) - 1):
+            ci, co = DEC_CH[i], DEC_CH[i + 1]
+            conv = (nn.ConvTranspose2d(ci, co, (8, 1), (4, 1), (2, 0)) if freq else nn.ConvTranspose1d(ci, co, 8, 4, 2))
+            # index 0: the ConvT; index 1: the GroupNorm (absent on the last level), as the reference's key names
+            self.layers.append(nn.Sequential(conv) if i == len(DEC_CH) - 2 else nn.Sequential(conv, nn.GroupNorm(1, co)))
+
+    def _resize(self, x: torch.Tensor, n: int) -> torch.Tensor:
+        if x.shape[2] == n:
+            return x
+        if self.freq:
+            return F.interpolate(x, size=(n, x.shape[3]), mode="bilinear", align_corners=False)
+        return F.interpolate(x, size=n, mode="linear", align_corners=False)
+
+    def forward(self, x: torch.Tensor, skips: List[torch.Tensor], targets: List[int]) -> torch.Tensor:
+        """skips / targets from the deepest level outwards"""
+        for i, layer in enumerate(self.layers):
+            x = layer(x)
+            if len(layer) > 1:
+                x = F.gelu(x)
+            if i < len(targets):
+                x = self._resize(x, targets[i])
+            if i < len(skips):
+                x = x + 0.1 * self._resize(skips[i][:, :x.shape[1]], x.shape[2])
+        return x
+
+
+class TrainableHead(nn.Module):
+    """(EncodedFeatures, text_emb (B, 512)) -> (B, 2, T): text conditioning, both decoders, the sigmoid mask on the
+    mixture's spectrogram, the inverse STFT and the time branch's denormalisation, summed (`ATHTDemucs_v2.py:282-324`).
+    Computes in the dtype of its parameters (features are cast to it)."""
+
+    def __init__(self):
+        super().__init__()
+        self.text_attn = _TextAttention()
+        self.freq_decoder = _Decoder(True)
+        self.time_decoder = _Decoder(False)
+        self.freq_out = nn.Conv2d(DEC_CH[-1], 2, 1)
+        self.time_out = nn.Conv1d(DEC_CH[-1], 2, 1)
+
+    @classmethod
+    def from_model(cls, model) -> "TrainableHead":
+        """The 50 head tensors of a loaded `AudioTextHTDemucs` (float32, on the CPU; move it with `.to`)"""
+        head = cls()
+        head.load_state_dict({k: torch.as_tensor(model._weights[k]).clone() for k, _ in head_keys()}, strict=True)
+        return head
+
+    def _ispec(self, z: torch.Tensor, length: int) -> torch.Tensor:
+        """demucs' `_ispec`: one zero bin on top, two zero frames on each side, the normalised Hann iSTFT, the crop"""
+        B, C, Fr, Ts = z.shape
+        z = F.pad(F.pad(z, (0, 0, 0, 1)), (2, 2))
+        pad = HOP // 2 * 3
+        le = HOP * int(math.ceil(length / HOP)) + 2 * pad
+        # the window is built in float32 and then cast, as demucs' `ispectro` does (`hann_window(n_fft).to(z.real)`): in
+        # float64 a window built there directly differs from it at 1e-8, which shows as 150 dB against the oracle
+        win = torch.hann_window(N_FFT).to(device=z.device, dtype=z.real.dtype)
+        x = torch.istft(z.reshape(B * C, Fr + 1, Ts + 4), N_FFT, HOP, window=win, win_length=N_FFT, normalized=True,
+                        length=le, center=True)
+        return x.reshape(B, C, le)[..., pad:pad + length]
+
+    def _cast(self, t: torch.Tensor) -> torch.Tensor:
+        p = self.freq_out.weight
+        return t.to(device=p.device, dtype=p.dtype)
+
+    def branches(self, f: EncodedFeatures, text_emb: torch.Tensor):
+        """(x_cond, xt_cond, freq_out(freq_decoder(..)), time_out(time_decoder(..))): everything before the mask"""
+        cast = self._cast
+        x_cond, xt_cond = self.text_attn(cast(f.x_enc), cast(f.xt_enc), cast(text_emb))
+        # frequency branch: logits on a (Ts, Ts) grid (the reference resizes the FREQUENCY axis to `lengths`, the frame
+        # counts)
+        xd = self.freq_decoder(x_cond, [cast(s) for s in f.skips[::-1]], list(f.lengths[::-1]))
+        xtd = self.time_decoder(xt_cond, [cast(s) for s in f.skips_t[::-1]], list(f.lengths_t[::-1]))
+        return x_cond, xt_cond, self.freq_out(xd), self.time_out(xtd)
+
+    def forward(self, f: EncodedFeatures, text_emb: torch.Tensor) -> torch.Tensor:
+        p = self.freq_out.weight
+        cast = self._cast
+        z = f.z.to(device=p.device, dtype=torch.complex128 if p.dtype == torch.float64 else torch.complex64)
+        _, _, xd, xtd = self.branches(f, text_emb)
+        # the logits stretched to the spectrogram's (2048, Ts)
+        mask = torch.sigmoid(F.interpolate(xd, size=(z.shape[2], z.shape[3]), mode="bilinear", align_corners=False))
+        # `mag[:, :2]` of the complex-as-channels magnitude is (Re, Im) of the LEFT channel: kept as the reference has it
+        mag_stereo = torch.stack((z[:, 0].real, z[:, 0].imag), dim=1)
+        phase = z / (mag_stereo + 1e-8)
+        freq_wav = self._ispec((mag_stereo * mask) * phase, f.length)
+        # time branch
+        if xtd.shape[-1] != f.length:
+            xtd = F.interpolate(xtd, size=f.length, mode="linear", align_corners=False)
+        return freq_wav + (xtd * cast(f.stdt) + cast(f.meant))
+
+
+class HeadTrainer(nn.Module):
+    """`model(mixture, prompts)` for `athd.train.train_epoch`: the native frozen half, then the torch head.  The native
+    model is a plain attribute (not a submodule): `parameters()`, `train()` and `eval()` are the head's."""
+
+    def __init__(self, model, head: Optional[TrainableHead] = None):
+        super().__init__()
+        object.__setattr__(self, "model", model)
+        if head is None:
+            if model.device is None:
+                model.to("cuda")
+            head = TrainableHead.from_model(model).to(model.device)
+        self.head = head
+
+    def forward(self, mixture: torch.Tensor, prompts) -> torch.Tensor:
+        feats = self.model.encode(mixture)
+        emb = self.model.embedder.rows(prompts, mixture.shape[0])
+        return self.head(feats, emb)
+
+    def state_dict(self, *args, **kwargs):
+        """the head's 50 reference keys (no `head.` prefix)"""
+        return self.head.state_dict(*args, **kwargs)
+
+    def load_state_dict(self, state_dict, strict: bool = True):
+        return self.head.load_state_dict(state_dict, strict=strict)
+
+    def sync(self):
+        """Load the head's current weights into the native model.  This re-finalises the native context (weights are
+        packed again), so call it once per validation, not per step."""
+        self.model.load_state_dict(self.head.state_dict())
+        return self

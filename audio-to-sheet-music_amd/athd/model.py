@@ -13,7 +13,7 @@ memory and the stream.  Additionally `forward_prompts(wav, prompts)` encodes onc
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Union
+from typing import Dict, List, NamedTuple, Optional, Union
 
 import numpy as np
 import torch
@@ -26,6 +26,34 @@ def _to_numpy(v) -> np.ndarray:
     if isinstance(v, torch.Tensor):
         return v.detach().to("cpu", torch.float32).numpy()
     return np.asarray(v, dtype=np.float32)
+
+
+SKIP_CH = (4, 48, 96, 192)      # channels the decoders read of encoder level i (the decoder level's own count)
+FREQ_ROWS = (512, 128, 32, 8)   # frequency rows of encoder level i
+
+
+class EncodedFeatures(NamedTuple):
+    """What the frozen half of the reference forward hands to its trainable half (`ATHTDemucs_v2.py:190-236, 261-279`),
+    float32 in the reference's layout.  `skips[i]` / `skips_t[i]` hold the first SKIP_CH[i] channels of the reference's
+    `saved[i]` / `saved_t[i]`: the decoders truncate every skip to that count and read nothing else."""
+    x_enc: torch.Tensor             # (B, 384, 8, Ts)
+    xt_enc: torch.Tensor            # (B, 384, L4)
+    skips: List[torch.Tensor]       # level order: (B, SKIP_CH[i], FREQ_ROWS[i], Ts)
+    skips_t: List[torch.Tensor]     # level order: (B, SKIP_CH[i], L[i+1])
+    z: torch.Tensor                 # (B, 2, 2048, Ts) complex64
+    meant: torch.Tensor             # (B, 1, 1)
+    stdt: torch.Tensor              # (B, 1, 1)
+    lengths: List[int]              # [Ts] * 4        (`:202`)
+    lengths_t: List[int]            # [T, L1, L2, L3] (`:198`)
+    length: int                     # T
+
+
+def time_lengths(T: int) -> List[int]:
+    """[T, L1, L2, L3, L4] with L[i+1] = ceil(L[i] / 4): the time encoder's level lengths"""
+    L = [int(T)]
+    for _ in range(4):
+        L.append(-(-L[-1] // 4))
+    return L
 
 
 class AudioTextHTDemucs:
@@ -186,6 +214,66 @@ class AudioTextHTDemucs:
         return out
 
     __call__ = forward
+
+    # ------------------------------------------------------------------ frozen features (head training)
+    def _feature_buffers(self, B: int, T: int):
+        """Fresh tensors for one athd_encode call and the athd_features struct that points at them"""
+        from . import native
+        Ts = -(-T // 1024)
+        L = time_lengths(T)
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        x_enc, xt_enc = new(B, 384, 8, Ts), new(B, 384, L[4])
+        skips = [new(B, SKIP_CH[i], FREQ_ROWS[i], Ts) for i in range(4)]
+        skips_t = [new(B, SKIP_CH[i], L[i + 1]) for i in range(4)]
+        zr, meant, stdt = new(B, 2, 2048, Ts, 2), new(B, 1, 1), new(B, 1, 1)
+        f = native.Features()
+        f.x_enc, f.xt_enc, f.z, f.meant, f.stdt = (t.data_ptr() for t in (x_enc, xt_enc, zr, meant, stdt))
+        for i in range(4):
+            f.skip_f[i], f.skip_t[i] = skips[i].data_ptr(), skips_t[i].data_ptr()
+        feats = EncodedFeatures(x_enc, xt_enc, skips, skips_t, torch.view_as_complex(zr), meant, stdt, [Ts] * 4, L[:4], T)
+        return f, feats
+
+    @torch.no_grad()
+    def encode(self, wav: torch.Tensor) -> EncodedFeatures:
+        """The frozen half of the forward (`ATHTDemucs_v2.py:261-279`: STFT, normalisation statistics, both encoders,
+        the cross-transformer) in libathd.so, returned as freshly allocated float32 tensors in the reference's layout
+        (athd_encode, include/athd.h) in either dtype mode.  No gradient flows into it, as in the reference."""
+        wav = self._check_wav(wav)
+        B, _, T = wav.shape
+        ctx = self._ensure_ctx()
+        f, feats = self._feature_buffers(B, T)
+        ws = self._workspace(ctx.encode_workspace_bytes(B, T))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        ctx.encode(wav.data_ptr(), B, T, f, ws.data_ptr(), ws.numel(), stream)
+        return feats
+
+    @torch.no_grad()
+    def capture_encode(self, wav: torch.Tensor, workspace: Optional[torch.Tensor] = None):
+        """`encode` on these exact buffers captured into one HIP graph, as `capture_prompts` does for the forward.
+        Returns (graph, features): the caller refreshes `wav` in place and replays; the feature tensors and the
+        workspace stay bound to the graph."""
+        if wav.dtype != torch.float32 or not wav.is_contiguous():
+            raise ValueError("capture_encode needs a contiguous float32 wav (B, 2, T)")
+        wav = self._check_wav(wav)
+        B, _, T = wav.shape
+        ctx = self._ensure_ctx()
+        f, feats = self._feature_buffers(B, T)
+        nbytes = ctx.encode_workspace_bytes(B, T)
+        if workspace is None:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        elif workspace.dtype != torch.uint8 or workspace.numel() < nbytes or workspace.device != self.device:
+            raise ValueError(f"workspace must be a uint8 tensor of >= {nbytes} bytes on {self.device}")
+        else:
+            ws = workspace
+        run = lambda: ctx.encode(wav.data_ptr(), B, T, f, ws.data_ptr(), ws.numel(),
+                                 torch.cuda.current_stream(self.device).cuda_stream)
+        run()                                   # eager once, as capture_prompts
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            run()
+        g._athd_keep = (wav, feats, ws)
+        return g, feats
 
     @torch.no_grad()
     def forward_prompts(self, wav: torch.Tensor, prompts: List[str], out: Optional[torch.Tensor] = None) -> torch.Tensor:

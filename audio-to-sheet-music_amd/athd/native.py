@@ -34,6 +34,17 @@ lib.athd_forward.restype = _c.c_int
 lib.athd_forward_prompts.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int,
                                      _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]
 lib.athd_forward_prompts.restype = _c.c_int
+class Features(_c.Structure):
+    """athd_features (include/athd.h): device pointers of the tensors athd_encode fills"""
+    _fields_ = [("x_enc", _c.c_void_p), ("xt_enc", _c.c_void_p), ("skip_f", _c.c_void_p * 4),
+                ("skip_t", _c.c_void_p * 4), ("z", _c.c_void_p), ("meant", _c.c_void_p), ("stdt", _c.c_void_p)]
+
+
+lib.athd_encode_workspace_bytes.argtypes = [_c.c_void_p, _c.c_int64, _c.c_int64]
+lib.athd_encode_workspace_bytes.restype = _c.c_size_t
+lib.athd_encode.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.POINTER(Features), _c.c_void_p,
+                            _c.c_size_t, _c.c_void_p]
+lib.athd_encode.restype = _c.c_int
 lib.athd_num_windows.argtypes = [_c.c_int64, _c.c_int64, _c.c_int64]
 lib.athd_num_windows.restype = _c.c_int64
 lib.athd_overlap_add.argtypes = [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int64,
@@ -132,7 +143,7 @@ EXPORTED = ["athd_version", "athd_create", "athd_set_weight", "athd_num_required
             "athd_text_finalize", "athd_text_workspace_bytes", "athd_text_encode", "athd_text_last_error",
             "athd_text_destroy", "athd_embed_compare_scratch_bytes", "athd_embed_compare",
             "athd_loss_grad_scratch_bytes", "athd_loss_grad_coef", "athd_loss_grad_apply",
-            "athd_gather_train_segments"]
+            "athd_gather_train_segments", "athd_encode_workspace_bytes", "athd_encode"]
 
 F32, BF16 = 0, 1
 
@@ -184,6 +195,13 @@ class Context:
     def forward_prompts(self, wav_ptr, B, T, table_ptr, P, out_ptr, ws_ptr, ws_bytes, stream_ptr):
         self._check(lib.athd_forward_prompts(self.h, wav_ptr, B, T, table_ptr, P, out_ptr, ws_ptr, ws_bytes,
                                              stream_ptr), "athd_forward_prompts")
+
+    def encode_workspace_bytes(self, B: int, T: int) -> int:
+        return int(lib.athd_encode_workspace_bytes(self.h, B, T))
+
+    def encode(self, wav_ptr, B, T, features: "Features", ws_ptr, ws_bytes, stream_ptr):
+        self._check(lib.athd_encode(self.h, wav_ptr, B, T, _c.byref(features), ws_ptr, ws_bytes, stream_ptr),
+                    "athd_encode")
 
     def profile_start(self, kernel: str | None = None):
         """Time every launch of `kernel` (rocprof symbol short form; None = all kernels) with HIP events."""

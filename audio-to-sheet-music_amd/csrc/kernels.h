@@ -301,4 +301,13 @@ size_t embed_compare_scratch_bytes(int n, int d);
 int embed_compare_launch(const float* emb, int n, int d, int64_t row_stride, const int32_t* category, float* normed,
                          float* sim, float* dist, double* stats, void* scratch, size_t scratch_bytes, hipStream_t s);
 
+// export.hip: the frozen features of athd_encode in the reference's (channel-first) layout, plain copies.
+// export_cf: channels [0, Cs) of a channels-last src [nb][rows][C] (f32, or bf16 widened exactly) -> f32 [nb][Cs][rows]
+// export_spec: specT [B][Tspec][2048][4] -> z [B][2][2048][Tspec][2] (re, im of the two audio channels)
+// export_norm: tnorm_std [B][2] = {mean, std} -> meant [B], stdt [B]
+// each returns -1 for a bad argument (nothing launched) or a HIP error
+int export_cf_launch(const void* src, int src_bf16, int64_t nb, int64_t rows, int C, int Cs, float* out, hipStream_t s);
+int export_spec_launch(const float* specT, int64_t B, int64_t Tspec, float* z, hipStream_t s);
+int export_norm_launch(const float* tnorm_std, int64_t B, float* meant, float* stdt, hipStream_t s);
+
 }  // namespace athd

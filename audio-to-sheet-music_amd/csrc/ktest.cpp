@@ -442,4 +442,17 @@ int kt_pos1d(float* out, int64_t T2, int64_t C, void* stream) {
     return (int)hipGetLastError();
 }
 
+// ---- the feature export of athd_encode (export.hip; tests/ktest_head.py) ----
+struct KtExportCf { void* src; int64_t src_bf16, nb, rows, C, Cs; void* out; };
+struct KtExportSpec { void* specT; int64_t B, Tspec; void* z; };
+int64_t kt_sizeof_export_cf() { return (int64_t)sizeof(KtExportCf); }
+int64_t kt_sizeof_export_spec() { return (int64_t)sizeof(KtExportSpec); }
+int kt_export_cf(const KtExportCf* k, void* stream) {
+    return export_cf_launch(k->src, (int)k->src_bf16, k->nb, k->rows, (int)k->C, (int)k->Cs, (float*)k->out,
+                            (hipStream_t)stream);
+}
+int kt_export_spec(const KtExportSpec* k, void* stream) {
+    return export_spec_launch((const float*)k->specT, k->B, k->Tspec, (float*)k->z, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -83,6 +83,38 @@ int athd_forward(athd_ctx* ctx, const float* wav, int64_t B, int64_t T, const fl
 int athd_forward_prompts(athd_ctx* ctx, const float* wav, int64_t B, int64_t T, const float* text_table, int P,
                          float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Frozen features for head training: the no_grad half of the forward (ATHTDemucs_v2.py:190-236, 261-279) ----
+ * The reference trains only text_attn / freq_decoder / time_decoder / freq_out / time_out; the HTDemucs encoders and
+ * the cross-transformer are frozen.  athd_encode runs exactly the encoder and transformer stages of athd_forward (same
+ * kernels, stream plan and runtime switches) and then copies what the trainable half reads into caller-owned tensors:
+ * float32, contiguous, in the reference's channel-first layout, whatever the context's dtype (bf16 activations are
+ * widened, which is exact).  With Ts = ceil(T / 1024), L[0] = T, L[i+1] = ceil(L[i] / 4), F[1..4] = {512, 128, 32, 8}
+ * and Ck = {4, 48, 96, 192}:
+ *   x_enc  (B, 384, 8, Ts), xt_enc (B, 384, L[4])    the transformer's outputs after the channel down-projection
+ *   skip_f[i] (B, Ck[i], F[i+1], Ts)                 channels [0, Ck[i]) of the reference's saved[i]
+ *   skip_t[i] (B, Ck[i], L[i+1])                     channels [0, Ck[i]) of saved_t[i]
+ *   z      (B, 2, 2048, Ts, 2)                       torch.view_as_real(z[:, :2]): re, im interleaved
+ *   meant, stdt (B)                                  wav.mean / wav.std (unbiased, torch.std) over (C, T)
+ * Only the first Ck[i] channels of a skip are exported because the decoders read nothing else: they truncate every skip
+ * to their own level's channel count (ATHTDemucs_v2.py:99-100, 134-135).
+ * Every member of `out` is a device pointer; a null one is ATHD_EINVAL.  ATHD_ESTATE before athd_finalize,
+ * ATHD_EWORKSPACE below athd_encode_workspace_bytes (today equal to athd_workspace_bytes(ctx, B, T, 1)).  Like
+ * athd_forward the call does not synchronise the host and creates no HIP objects, so it can be graph-captured from the
+ * first call; the time branch runs on the context's second stream and is joined before the copies, which run on the
+ * caller's stream: every exported tensor is complete in the order of that stream. */
+typedef struct athd_features {
+    float* x_enc;
+    float* xt_enc;
+    float* skip_f[4];
+    float* skip_t[4];
+    float* z;
+    float* meant;
+    float* stdt;
+} athd_features;
+size_t athd_encode_workspace_bytes(athd_ctx* ctx, int64_t B, int64_t T);
+int athd_encode(athd_ctx* ctx, const float* wav, int64_t B, int64_t T, const athd_features* out, void* workspace,
+                size_t workspace_bytes, void* stream);
+
 /* ---- Track level: the window loop of test_inference.py:92-141 and sdr_loss (src/loss.py:9-30) ----
  * Windows: start_k = k*hop with hop = chunk_len - overlap, for k = 0 .. athd_num_windows()-1 (while start < length),
  * end_k = min(start_k + chunk_len, length).  Window k is faded by torchaudio Fade(fade_in = k ? overlap : 0,
