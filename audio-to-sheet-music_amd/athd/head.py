@@ -4,7 +4,8 @@ The reference trains only `text_attn`, `freq_decoder`, `time_decoder`, `freq_out
 the HTDemucs encoders, the cross-transformer and CLAP run frozen under `no_grad` (`:277-279`).  `AudioTextHTDemucs.encode`
 (athd/model.py, `athd_encode`) computes that frozen half in libathd.so; `TrainableHead` is the rest (`:21-139, 282-324`),
 differentiable by autograd on any device and dtype; `HeadTrainer` joins the two behind the `model(mixture, prompts)`
-call that `athd.train.train_epoch` expects.  The model's backward stays torch's.
+call that `athd.train.train_epoch` expects.  The model's backward stays torch's, except for the output
+stage (mask, iSTFT, denormalisation), which `native_output=True` runs natively in both directions (`NativeOutputStage`).
 
 `TrainableHead.state_dict()` has exactly the 50 reference key names and shapes outside `htdemucs.` / `clap.`
 (`athd.weights.hot_path_spec`), so a trained head drops into a reference-format checkpoint and loads straight back into
@@ -19,6 +20,7 @@ in the reference: an optimizer with weight decay moves them exactly as it does t
 from __future__ import annotations
 
 import math
+import weakref
 from typing import List, Optional
 
 import torch
@@ -99,18 +101,98 @@ class _Decoder(nn.Module):
         return x
 
 
+class NativeOutputStage(torch.autograd.Function):
+    """The output stage of `TrainableHead.forward` in libathd.so, both directions: `(xd (B, 2, Ts, Ts), xtd (B, 2, T))
+    -> (B, 2, T)` = iSTFT(sigmoid mask on the spectrogram) + (xtd stdt + meant) by `athd_head_output` (the inference
+    path's fused kernel, no 2048 x Ts intermediate in memory), and the gradient with respect to the logits by
+    `athd_head_output_backward` (an STFT of the incoming gradient, include/athd.h).  The permutes to the kernels'
+    frame-major layouts are torch's.  `spec` is `athd_pack_spectrum` of the features' `z`; it, `meant` and `stdt` get no
+    gradient (they come from the frozen half)."""
+
+    @staticmethod
+    def forward(ctx, xd, xtd, spec, meant, stdt, nctx):
+        B, _, T = xtd.shape
+        # (.float(): under autocast the 1x1 convolutions hand over half-precision tensors)
+        logits = xd.detach().float().permute(0, 3, 2, 1).contiguous()      # (B, frame, row, channel)
+        xt = xtd.detach().float().transpose(1, 2).contiguous()             # (B, T, 2)
+        tnorm = torch.stack((meant.reshape(B), stdt.reshape(B)), dim=1).float().contiguous()
+        out = torch.empty((B, 2, T), dtype=torch.float32, device=xd.device)
+        ws = torch.empty(max(nctx.head_output_workspace_bytes(B, T), 16), dtype=torch.uint8, device=xd.device)
+        stream = torch.cuda.current_stream(xd.device).cuda_stream
+        nctx.head_output(logits.data_ptr(), spec.data_ptr(), xt.data_ptr(), tnorm.data_ptr(), B, T, out.data_ptr(),
+                         ws.data_ptr(), ws.numel(), stream)
+        ctx.save_for_backward(logits, spec, stdt)
+        ctx.nctx, ctx.T, ctx.dtypes = nctx, T, (xd.dtype, xtd.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, spec, stdt = ctx.saved_tensors
+        g = g.float().contiguous()
+        grad_logits = torch.empty_like(logits)
+        ctx.nctx.head_output_backward(g.data_ptr(), logits.data_ptr(), spec.data_ptr(), logits.shape[0], ctx.T,
+                                      grad_logits.data_ptr(), torch.cuda.current_stream(g.device).cuda_stream)
+        return (grad_logits.permute(0, 3, 2, 1).to(ctx.dtypes[0]), (g * stdt.reshape(-1, 1, 1)).to(ctx.dtypes[1]), None,
+                None, None, None)
+
+
 class TrainableHead(nn.Module):
     """(EncodedFeatures, text_emb (B, 512)) -> (B, 2, T): text conditioning, both decoders, the sigmoid mask on the
     mixture's spectrogram, the inverse STFT and the time branch's denormalisation, summed (`ATHTDemucs_v2.py:282-324`).
-    Computes in the dtype of its parameters (features are cast to it)."""
+    Computes in the dtype of its parameters (features are cast to it).
 
-    def __init__(self):
+    `native_output=True` runs the last stage (mask, iSTFT, denormalisation) and its gradient in libathd.so
+    (`NativeOutputStage`) instead of as torch ops.  It needs the native model for its context (`bind`; `HeadTrainer`
+    does that), float32 parameters on the model's GPU and at most 2048 frames, and raises otherwise: a float64 or CPU
+    head uses the torch stage by leaving the option off, never by a silent fallback."""
+
+    def __init__(self, native_output: bool = False):
         super().__init__()
         self.text_attn = _TextAttention()
         self.freq_decoder = _Decoder(True)
         self.time_decoder = _Decoder(False)
         self.freq_out = nn.Conv2d(DEC_CH[-1], 2, 1)
         self.time_out = nn.Conv1d(DEC_CH[-1], 2, 1)
+        self.native_output = bool(native_output)
+        object.__setattr__(self, "_native_model", None)      # a plain attribute, not a submodule
+        object.__setattr__(self, "_spec_cache", None)        # (weakref to z, its version, packed spectrum)
+
+    def bind(self, model) -> "TrainableHead":
+        """The native `AudioTextHTDemucs` whose context (FFT and window tables, dtype) the native output stage uses.  The
+        context is looked up per call, so `HeadTrainer.sync()` (which re-finalises it) needs no re-binding."""
+        object.__setattr__(self, "_native_model", model)
+        return self
+
+    def packed_spectrum(self, z: torch.Tensor) -> torch.Tensor:
+        """`athd_pack_spectrum` of an `EncodedFeatures.z`, (B, Ts, 2048, 4) float32; computed once per `z` tensor (the
+        last one is kept, keyed on the tensor's identity and version)"""
+        c = self._spec_cache
+        if c is not None and c[0]() is z and c[1] == z._version:
+            return c[2]
+        B, _, _, Ts = z.shape
+        zr = torch.view_as_real(z).contiguous()
+        spec = torch.empty((B, Ts, 2048, 4), dtype=torch.float32, device=z.device)
+        self._native_model._ensure_ctx().pack_spectrum(zr.data_ptr(), B, Ts, spec.data_ptr(),
+                                                       torch.cuda.current_stream(z.device).cuda_stream)
+        object.__setattr__(self, "_spec_cache", (weakref.ref(z), z._version, spec))
+        return spec
+
+    def _native_stage(self, f: EncodedFeatures, xd: torch.Tensor, xtd: torch.Tensor) -> torch.Tensor:
+        model, p = self._native_model, self.freq_out.weight
+        if model is None:
+            raise RuntimeError("native_output=True needs the native model: call head.bind(model) (HeadTrainer does)")
+        if p.dtype != torch.float32 or p.device.type != "cuda" or p.device != model.device:
+            raise RuntimeError(f"native_output=True needs float32 parameters on the model's device {model.device}, got "
+                               f"{p.dtype} on {p.device}; leave the option off for the torch output stage")
+        z = f.z
+        if z.dtype != torch.complex64 or z.device != p.device or z.shape[1:3] != (2, 2048):
+            raise RuntimeError("native_output=True needs the features' z as complex64 (B, 2, 2048, Ts) on the model's "
+                               "device")
+        if z.shape[3] > 2048 or z.shape[3] != -(-f.length // HOP):
+            raise RuntimeError(f"native_output=True covers segments of at most 2048 frames, got {z.shape[3]} frames "
+                               f"for {f.length} samples")
+        return NativeOutputStage.apply(xd, xtd, self.packed_spectrum(z), self._cast(f.meant), self._cast(f.stdt),
+                                       model._ensure_ctx())
 
     @classmethod
     def from_model(cls, model) -> "TrainableHead":
@@ -149,8 +231,13 @@ class TrainableHead(nn.Module):
     def forward(self, f: EncodedFeatures, text_emb: torch.Tensor) -> torch.Tensor:
         p = self.freq_out.weight
         cast = self._cast
-        z = f.z.to(device=p.device, dtype=torch.complex128 if p.dtype == torch.float64 else torch.complex64)
         _, _, xd, xtd = self.branches(f, text_emb)
+        if self.native_output:
+            # (the time branch's resize, when the head emits another length, stays torch's, in front of the Function)
+            if xtd.shape[-1] != f.length:
+                xtd = F.interpolate(xtd, size=f.length, mode="linear", align_corners=False)
+            return self._native_stage(f, xd, xtd)
+        z = f.z.to(device=p.device, dtype=torch.complex128 if p.dtype == torch.float64 else torch.complex64)
         # the logits stretched to the spectrogram's (2048, Ts)
         mask = torch.sigmoid(F.interpolate(xd, size=(z.shape[2], z.shape[3]), mode="bilinear", align_corners=False))
         # `mag[:, :2]` of the complex-as-channels magnitude is (Re, Im) of the LEFT channel: kept as the reference has it
@@ -167,13 +254,18 @@ class HeadTrainer(nn.Module):
     """`model(mixture, prompts)` for `athd.train.train_epoch`: the native frozen half, then the torch head.  The native
     model is a plain attribute (not a submodule): `parameters()`, `train()` and `eval()` are the head's."""
 
-    def __init__(self, model, head: Optional[TrainableHead] = None):
+    def __init__(self, model, head: Optional[TrainableHead] = None, native_output: bool = False):
         super().__init__()
         object.__setattr__(self, "model", model)
         if head is None:
             if model.device is None:
                 model.to("cuda")
             head = TrainableHead.from_model(model).to(model.device)
+        # native_output: the head's last stage and its gradient in libathd.so (TrainableHead); a head that was built
+        # with the option keeps it.  Only such a head holds a reference to the native model.
+        if native_output or head.native_output:
+            head.native_output = True
+            head.bind(model)
         self.head = head
 
     def forward(self, mixture: torch.Tensor, prompts) -> torch.Tensor:

@@ -45,6 +45,16 @@ lib.athd_encode_workspace_bytes.restype = _c.c_size_t
 lib.athd_encode.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.POINTER(Features), _c.c_void_p,
                             _c.c_size_t, _c.c_void_p]
 lib.athd_encode.restype = _c.c_int
+lib.athd_pack_spectrum.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p]
+lib.athd_pack_spectrum.restype = _c.c_int
+lib.athd_head_output_workspace_bytes.argtypes = [_c.c_int64, _c.c_int64]
+lib.athd_head_output_workspace_bytes.restype = _c.c_size_t
+lib.athd_head_output.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64,
+                                 _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]
+lib.athd_head_output.restype = _c.c_int
+lib.athd_head_output_backward.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64,
+                                          _c.c_void_p, _c.c_void_p]
+lib.athd_head_output_backward.restype = _c.c_int
 lib.athd_num_windows.argtypes = [_c.c_int64, _c.c_int64, _c.c_int64]
 lib.athd_num_windows.restype = _c.c_int64
 lib.athd_overlap_add.argtypes = [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int64,
@@ -143,7 +153,8 @@ EXPORTED = ["athd_version", "athd_create", "athd_set_weight", "athd_num_required
             "athd_text_finalize", "athd_text_workspace_bytes", "athd_text_encode", "athd_text_last_error",
             "athd_text_destroy", "athd_embed_compare_scratch_bytes", "athd_embed_compare",
             "athd_loss_grad_scratch_bytes", "athd_loss_grad_coef", "athd_loss_grad_apply",
-            "athd_gather_train_segments", "athd_encode_workspace_bytes", "athd_encode"]
+            "athd_gather_train_segments", "athd_encode_workspace_bytes", "athd_encode", "athd_pack_spectrum",
+            "athd_head_output_workspace_bytes", "athd_head_output", "athd_head_output_backward"]
 
 F32, BF16 = 0, 1
 
@@ -202,6 +213,21 @@ class Context:
     def encode(self, wav_ptr, B, T, features: "Features", ws_ptr, ws_bytes, stream_ptr):
         self._check(lib.athd_encode(self.h, wav_ptr, B, T, _c.byref(features), ws_ptr, ws_bytes, stream_ptr),
                     "athd_encode")
+
+    def pack_spectrum(self, z_ptr, B, Ts, spec_ptr, stream_ptr):
+        self._check(lib.athd_pack_spectrum(self.h, z_ptr, B, Ts, spec_ptr, stream_ptr), "athd_pack_spectrum")
+
+    @staticmethod
+    def head_output_workspace_bytes(B: int, T: int) -> int:
+        return int(lib.athd_head_output_workspace_bytes(B, T))
+
+    def head_output(self, logits_ptr, spec_ptr, xt_ptr, tnorm_ptr, B, T, out_ptr, ws_ptr, ws_bytes, stream_ptr):
+        self._check(lib.athd_head_output(self.h, logits_ptr, spec_ptr, xt_ptr, tnorm_ptr, B, T, out_ptr, ws_ptr,
+                                         ws_bytes, stream_ptr), "athd_head_output")
+
+    def head_output_backward(self, grad_out_ptr, logits_ptr, spec_ptr, B, T, grad_logits_ptr, stream_ptr):
+        self._check(lib.athd_head_output_backward(self.h, grad_out_ptr, logits_ptr, spec_ptr, B, T, grad_logits_ptr,
+                                                  stream_ptr), "athd_head_output_backward")
 
     def profile_start(self, kernel: str | None = None):
         """Time every launch of `kernel` (rocprof symbol short form; None = all kernels) with HIP events."""

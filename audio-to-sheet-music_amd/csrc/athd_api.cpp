@@ -140,7 +140,7 @@ const std::vector<std::pair<std::string, std::vector<int64_t>>>& keys() {
 // =============================================================================================== ABI
 extern "C" {
 
-int athd_version(void) { return 104; }
+int athd_version(void) { return 105; }
 
 int athd_num_required_keys(void) { return (int)keys().size(); }
 

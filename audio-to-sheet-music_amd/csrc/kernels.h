@@ -310,4 +310,13 @@ int export_cf_launch(const void* src, int src_bf16, int64_t nb, int64_t rows, in
 int export_spec_launch(const float* specT, int64_t B, int64_t Tspec, float* z, hipStream_t s);
 int export_norm_launch(const float* tnorm_std, int64_t B, float* meant, float* stdt, hipStream_t s);
 
+// head_grad.hip: head training's output stage.
+// pack_spec: z [B][2][2048][Tspec][2] -> specT [B][Tspec][2048][4], the inverse of export_spec
+// head_grad: the adjoint of istft_ola with P = 1 with respect to its logits: g [B][2][T] = dL/dout, fo [B][Tspec][Tspec][2]
+// and specT as the forward read them -> gfo [B][Tspec][Tspec][2], every element written; Tspec = ceil(T / 1024) <= 2048
+// each returns -1 for a bad argument (nothing launched) or a HIP error
+int pack_spec_launch(const float* z, int64_t B, int64_t Tspec, float* specT, hipStream_t s);
+int head_grad_launch(const float* g, const float* fo, const float* specT, int64_t B, int Tspec, int64_t T,
+                     const float2* tw, const float* win, const float* win2, float* gfo, hipStream_t s);
+
 }  // namespace athd

@@ -455,4 +455,13 @@ int kt_export_spec(const KtExportSpec* k, void* stream) {
     return export_spec_launch((const float*)k->specT, k->B, k->Tspec, (float*)k->z, (hipStream_t)stream);
 }
 
+// ---- head training's output stage (head_grad.hip; tests/test_gpu_head_output.py) ----
+// the device tables of a finalized context {tw, tw64, win, win2}, so that kt_istft_ola can run on the very tables
+// athd_head_output uses
+int kt_ctx_tables(const athd_ctx* c, void** out) {
+    if (!c || !c->finalized || !out) return -1;
+    out[0] = c->tw; out[1] = c->tw64; out[2] = c->win; out[3] = c->win2;
+    return 0;
+}
+
 }  // extern "C"

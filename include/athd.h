@@ -115,6 +115,42 @@ size_t athd_encode_workspace_bytes(athd_ctx* ctx, int64_t B, int64_t T);
 int athd_encode(athd_ctx* ctx, const float* wav, int64_t B, int64_t T, const athd_features* out, void* workspace,
                 size_t workspace_bytes, void* stream);
 
+/* ---- Head training's output stage: the mask, the inverse STFT and the time branch's denormalisation
+ * (ATHTDemucs_v2.py:303-324) in both directions ----
+ * What the trainable half ends with, fed by athd_encode's z, meant and stdt and by the head's two 1x1 output
+ * convolutions.  With Ts = ceil(T / 1024), per item and audio channel c:
+ *   mask_c = sigmoid(resize(logits_c))     the logits' Ts rows stretched linearly to 2048 bins (align_corners = False)
+ *   X_c    = (m_c mask_c) z_c / (m_c + 1e-8),  (m_0, m_1) = (Re z_0, Im z_0) as the reference has it
+ *   out    = istft(X) + (xt stdt + meant)      demucs' _ispec: Hann 4096 / 1024, normalized, cropped to T
+ * The three entries take the context for its FFT and window tables and its dtype; they read no weight.  All enqueue on
+ * the caller's stream, do not synchronise the host and create no HIP object, so they can be graph-captured from the
+ * first call.  ATHD_ESTATE before athd_finalize; ATHD_EINVAL for a null pointer, B outside [1, 65535], T < 1 or more
+ * than 2048 frames (T > 2097152, 47 s: the resize would turn into a downsample whose adjoint is not implemented);
+ * ATHD_EWORKSPACE below athd_head_output_workspace_bytes (which is 0 for shapes out of range).  Arguments are checked
+ * in that order before anything is read or written.
+ *
+ * athd_pack_spectrum: z (B, 2, 2048, Ts, 2) as athd_encode exports it -> spec (B, Ts, 2048, 4) = {Re L, Im L, Re R,
+ * Im R}, frame-major: the layout the two entries below read, a plain copy (bit-exact).  Once per batch.
+ *
+ * athd_head_output: logits (B, Ts, Ts, 2) = [frame][row][channel], xt (B, T, 2), tnorm (B, 2) = {meant, stdt} ->
+ * out (B, 2, T).  This is the inference path's own fused kernel with one prompt per segment (no frame tensor in
+ * memory), bit-identical to athd_forward's last stage on the same buffers: an ATHD_F32 context runs the FFT in double
+ * with IEEE exp and divisions, an ATHD_BF16 context the float FFT with v_exp / v_rcp.  ws: device, 16-byte aligned,
+ * not initialised by the caller.
+ *
+ * athd_head_output_backward: grad_out (B, 2, T) = dL/dout, channel-first and contiguous (what athd_loss_grad_apply
+ * writes), with the logits and spec of the forward -> grad_logits (B, Ts, Ts, 2) = dL/dlogits.  The adjoint of the
+ * inverse STFT is an STFT of grad_out / envelope; the mask is recomputed from the logits (nothing is saved by the
+ * forward).  One kernel, f32 arithmetic with IEEE exp and divisions in both dtype modes; every element of grad_logits
+ * is written exactly once, sums run in a fixed order and there are no atomics: the same bits on every run and under
+ * graph replay.  dL/dxt needs no kernel: it is grad_out * stdt, transposed. */
+int athd_pack_spectrum(athd_ctx* ctx, const float* z, int64_t B, int64_t Ts, float* spec, void* stream);
+size_t athd_head_output_workspace_bytes(int64_t B, int64_t T);
+int athd_head_output(athd_ctx* ctx, const float* logits, const float* spec, const float* xt, const float* tnorm,
+                     int64_t B, int64_t T, float* out, void* ws, size_t ws_bytes, void* stream);
+int athd_head_output_backward(athd_ctx* ctx, const float* grad_out, const float* logits, const float* spec, int64_t B,
+                              int64_t T, float* grad_logits, void* stream);
+
 /* ---- Track level: the window loop of test_inference.py:92-141 and sdr_loss (src/loss.py:9-30) ----
  * Windows: start_k = k*hop with hop = chunk_len - overlap, for k = 0 .. athd_num_windows()-1 (while start < length),
  * end_k = min(start_k + chunk_len, length).  Window k is faded by torchaudio Fade(fade_in = k ? overlap : 0,
