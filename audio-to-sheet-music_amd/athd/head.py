@@ -5,7 +5,8 @@ the HTDemucs encoders, the cross-transformer and CLAP run frozen under `no_grad`
 (athd/model.py, `athd_encode`) computes that frozen half in libathd.so; `TrainableHead` is the rest (`:21-139, 282-324`),
 differentiable by autograd on any device and dtype; `HeadTrainer` joins the two behind the `model(mixture, prompts)`
 call that `athd.train.train_epoch` expects.  The model's backward stays torch's, except for the output
-stage (mask, iSTFT, denormalisation), which `native_output=True` runs natively in both directions (`NativeOutputStage`).
+stage (mask, iSTFT, denormalisation), which `native_output=True` runs natively in both directions (`NativeOutputStage`),
+and the text-conditioning stage, which `native_cond=True` does (`NativeCondStage`).
 
 `TrainableHead.state_dict()` has exactly the 50 reference key names and shapes outside `htdemucs.` / `clap.`
 (`athd.weights.hot_path_spec`), so a trained head drops into a reference-format checkpoint and loads straight back into
@@ -15,7 +16,9 @@ Dead parameters.  The text cross-attention has ONE key (the prompt embedding), s
 attention output does not depend on the query or the key.  `text_attn.q_proj.*`, `text_attn.k_proj.*`,
 `text_attn.norm_q.*` and the query and key thirds of `text_attn.attn.in_proj_*` therefore get a mathematically zero
 gradient (rounding leaves values around 1e-24 of the live gradients).  They stay parameters with `requires_grad=True`, as
-in the reference: an optimizer with weight decay moves them exactly as it does there.
+in the reference: an optimizer with weight decay moves them exactly as it does there.  The native conditioning stage
+never computes the query side; it hands these tensors exact zeros as gradients (`_DeadParams`), so `.grad` is a tensor,
+not `None`, and such an optimizer does not skip them.
 """
 from __future__ import annotations
 
@@ -58,6 +61,29 @@ class _TextAttention(nn.Module):
         u = seq + a
         return self.norm_out(u + self.out_mlp(u))
 
+    def attn_vector(self, text: torch.Tensor) -> torch.Tensor:
+        """text (B, text_dim) -> (B, D): what `attn` returns for every row when there is one key (the softmax is 1):
+        out_proj(in_proj_v(v_proj(text))).  The slices hand the query and key thirds of `in_proj_*` exact zeros."""
+        D = self.attn.embed_dim
+        v = F.linear(text, self.v_proj.weight, self.v_proj.bias)
+        v = F.linear(v, self.attn.in_proj_weight[2 * D:], self.attn.in_proj_bias[2 * D:])
+        return F.linear(v, self.attn.out_proj.weight, self.attn.out_proj.bias)
+
+    def dead_parameters(self):
+        """the six tensors the output does not depend on (the query and key thirds of `in_proj_*` are the other dead
+        values)"""
+        return [self.q_proj.weight, self.q_proj.bias, self.k_proj.weight, self.k_proj.bias, self.norm_q.weight,
+                self.norm_q.bias]
+
+    def forward_native(self, x: torch.Tensor, xt: torch.Tensor, text_emb: torch.Tensor, nctx):
+        """`forward` through `NativeCondStage`: x, xt contiguous float32 channel-first; float32 whatever autocast says"""
+        with torch.autocast(device_type=x.device.type, enabled=False):
+            a = _DeadParams.apply(self.attn_vector(text_emb.reshape(text_emb.shape[0], -1).float()),
+                                  *self.dead_parameters())
+            w = (self.out_mlp[0].weight, self.out_mlp[0].bias, self.out_mlp[2].weight, self.out_mlp[2].bias,
+                 self.norm_out.weight, self.norm_out.bias)
+            return NativeCondStage.apply(x, a, *w, nctx), NativeCondStage.apply(xt, a, *w, nctx)
+
     def forward(self, x: torch.Tensor, xt: torch.Tensor, text_emb: torch.Tensor):
         text = text_emb[:, None, :] if text_emb.dim() == 2 else text_emb
         B, C, Fr, Ts = x.shape
@@ -99,6 +125,56 @@ class _Decoder(nn.Module):
             if i < len(skips):
                 x = x + 0.1 * self._resize(skips[i][:, :x.shape[1]], x.shape[2])
         return x
+
+
+class _DeadParams(torch.autograd.Function):
+    """`a` unchanged, with the dead parameters attached to the graph: the backward hands each of them an exact zero
+    tensor.  Without this the native conditioning stage, which never touches the query side, would leave their `.grad`
+    at `None`, and an optimizer skips a parameter without a gradient, weight decay included."""
+
+    @staticmethod
+    def forward(ctx, a, *dead):
+        ctx.save_for_backward(*dead)
+        return a.view_as(a)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g,) + tuple(torch.zeros_like(p) for p in ctx.saved_tensors)
+
+
+class NativeCondStage(torch.autograd.Function):
+    """The text-conditioning stage after the attention vector, in libathd.so, both directions (`athd_head_cond`,
+    `athd_head_cond_backward`, include/athd.h): `x (B, 384, ...)` channel-first float32 as `athd_encode` exports it,
+    `a (B, 384)` the attention output per item, `out_mlp.0`, `out_mlp.2` and `norm_out` -> `y` of x's shape =
+    `norm_out(u + out_mlp(u))`, `u = x + a`.  `x` gets no gradient (it comes from the frozen half).  The backward
+    recomputes the forward from `x`: besides `x`, `a` and the six parameters nothing is saved, no (rows x 384) tensor; its
+    workspace lives only inside the backward call."""
+
+    @staticmethod
+    def forward(ctx, x, a, w0, b0, w2, b2, gamma, beta, nctx):
+        B = x.shape[0]
+        N = x.numel() // (B * MODEL_DIM)
+        t = [p.detach().float().contiguous() for p in (a, w0, b0, w2, b2, gamma, beta)]
+        y = torch.empty_like(x)
+        nctx.head_cond(x.data_ptr(), *[p.data_ptr() for p in t], B, N, y.data_ptr(), 0, 0,
+                       torch.cuda.current_stream(x.device).cuda_stream)
+        ctx.save_for_backward(x, *t[:6])
+        ctx.nctx, ctx.BN, ctx.dtypes = nctx, (B, N), [p.dtype for p in (a, w0, b0, w2, b2, gamma, beta)]
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, a, w0, b0, w2, b2, gamma = ctx.saved_tensors
+        B, N = ctx.BN
+        g = g.float().contiguous()
+        grads = [torch.empty_like(p) for p in (a, w0, b0, w2, b2, gamma, gamma)]
+        ga, gw0, gb0, gw2, gb2, ggamma, gbeta = grads
+        ws = torch.empty(max(ctx.nctx.head_cond_workspace_bytes(B, N), 16), dtype=torch.uint8, device=g.device)
+        ctx.nctx.head_cond_backward(g.data_ptr(), x.data_ptr(), a.data_ptr(), w0.data_ptr(), b0.data_ptr(), w2.data_ptr(),
+                                    b2.data_ptr(), gamma.data_ptr(), B, N, gw0.data_ptr(), gb0.data_ptr(), gw2.data_ptr(),
+                                    gb2.data_ptr(), ggamma.data_ptr(), gbeta.data_ptr(), ga.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), torch.cuda.current_stream(g.device).cuda_stream)
+        return (None,) + tuple(t.to(d) for t, d in zip(grads, ctx.dtypes)) + (None,)
 
 
 class NativeOutputStage(torch.autograd.Function):
@@ -144,9 +220,15 @@ class TrainableHead(nn.Module):
     `native_output=True` runs the last stage (mask, iSTFT, denormalisation) and its gradient in libathd.so
     (`NativeOutputStage`) instead of as torch ops.  It needs the native model for its context (`bind`; `HeadTrainer`
     does that), float32 parameters on the model's GPU and at most 2048 frames, and raises otherwise: a float64 or CPU
-    head uses the torch stage by leaving the option off, never by a silent fallback."""
+    head uses the torch stage by leaving the option off, never by a silent fallback.
 
-    def __init__(self, native_output: bool = False):
+    `native_cond=True` does the same for the first stage, the text conditioning (`NativeCondStage`: the residual MLP and
+    LayerNorm on the features' channel-first layout, no permute, and their gradients; the attention vector per item stays
+    torch's).  Same requirements (bound model, float32 parameters on its GPU) plus contiguous float32 features on that
+    GPU, as `encode` returns them; it raises otherwise.  Under autocast it computes and returns float32.  The two options
+    are independent and compose."""
+
+    def __init__(self, native_output: bool = False, native_cond: bool = False):
         super().__init__()
         self.text_attn = _TextAttention()
         self.freq_decoder = _Decoder(True)
@@ -154,6 +236,7 @@ class TrainableHead(nn.Module):
         self.freq_out = nn.Conv2d(DEC_CH[-1], 2, 1)
         self.time_out = nn.Conv1d(DEC_CH[-1], 2, 1)
         self.native_output = bool(native_output)
+        self.native_cond = bool(native_cond)
         object.__setattr__(self, "_native_model", None)      # a plain attribute, not a submodule
         object.__setattr__(self, "_spec_cache", None)        # (weakref to z, its version, packed spectrum)
 
@@ -194,6 +277,20 @@ class TrainableHead(nn.Module):
         return NativeOutputStage.apply(xd, xtd, self.packed_spectrum(z), self._cast(f.meant), self._cast(f.stdt),
                                        model._ensure_ctx())
 
+    def _native_cond_stage(self, f: EncodedFeatures, text_emb: torch.Tensor):
+        model, p = self._native_model, self.text_attn.norm_out.weight
+        if model is None:
+            raise RuntimeError("native_cond=True needs the native model: call head.bind(model) (HeadTrainer does)")
+        if p.dtype != torch.float32 or p.device.type != "cuda" or p.device != model.device:
+            raise RuntimeError(f"native_cond=True needs float32 parameters on the model's device {model.device}, got "
+                               f"{p.dtype} on {p.device}; leave the option off for the torch conditioning stage")
+        for name, t in (("x_enc", f.x_enc), ("xt_enc", f.xt_enc)):
+            if (t.dtype != torch.float32 or t.device != p.device or not t.is_contiguous() or t.dim() < 3
+                    or t.shape[1] != MODEL_DIM or t.numel() == 0):
+                raise RuntimeError(f"native_cond=True needs the features' {name} as contiguous float32 (B, {MODEL_DIM}, "
+                                   f"...) on the model's device, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return self.text_attn.forward_native(f.x_enc, f.xt_enc, text_emb.to(p.device), model._ensure_ctx())
+
     @classmethod
     def from_model(cls, model) -> "TrainableHead":
         """The 50 head tensors of a loaded `AudioTextHTDemucs` (float32, on the CPU; move it with `.to`)"""
@@ -221,7 +318,10 @@ class TrainableHead(nn.Module):
     def branches(self, f: EncodedFeatures, text_emb: torch.Tensor):
         """(x_cond, xt_cond, freq_out(freq_decoder(..)), time_out(time_decoder(..))): everything before the mask"""
         cast = self._cast
-        x_cond, xt_cond = self.text_attn(cast(f.x_enc), cast(f.xt_enc), cast(text_emb))
+        if self.native_cond:
+            x_cond, xt_cond = self._native_cond_stage(f, text_emb)
+        else:
+            x_cond, xt_cond = self.text_attn(cast(f.x_enc), cast(f.xt_enc), cast(text_emb))
         # frequency branch: logits on a (Ts, Ts) grid (the reference resizes the FREQUENCY axis to `lengths`, the frame
         # counts)
         xd = self.freq_decoder(x_cond, [cast(s) for s in f.skips[::-1]], list(f.lengths[::-1]))
@@ -254,17 +354,19 @@ class HeadTrainer(nn.Module):
     """`model(mixture, prompts)` for `athd.train.train_epoch`: the native frozen half, then the torch head.  The native
     model is a plain attribute (not a submodule): `parameters()`, `train()` and `eval()` are the head's."""
 
-    def __init__(self, model, head: Optional[TrainableHead] = None, native_output: bool = False):
+    def __init__(self, model, head: Optional[TrainableHead] = None, native_output: bool = False,
+                 native_cond: bool = False):
         super().__init__()
         object.__setattr__(self, "model", model)
         if head is None:
             if model.device is None:
                 model.to("cuda")
             head = TrainableHead.from_model(model).to(model.device)
-        # native_output: the head's last stage and its gradient in libathd.so (TrainableHead); a head that was built
-        # with the option keeps it.  Only such a head holds a reference to the native model.
-        if native_output or head.native_output:
-            head.native_output = True
+        # native_output / native_cond: the head's last / first stage and its gradient in libathd.so (TrainableHead); a
+        # head that was built with an option keeps it.  Only such a head holds a reference to the native model.
+        head.native_output = bool(native_output or head.native_output)
+        head.native_cond = bool(native_cond or head.native_cond)
+        if head.native_output or head.native_cond:
             head.bind(model)
         self.head = head
 

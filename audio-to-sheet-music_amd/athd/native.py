@@ -55,6 +55,14 @@ lib.athd_head_output.restype = _c.c_int
 lib.athd_head_output_backward.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64,
                                           _c.c_void_p, _c.c_void_p]
 lib.athd_head_output_backward.restype = _c.c_int
+lib.athd_head_cond_workspace_bytes.argtypes = [_c.c_int64, _c.c_int64]
+lib.athd_head_cond_workspace_bytes.restype = _c.c_size_t
+lib.athd_head_cond.argtypes = [_c.c_void_p] + [_c.c_void_p] * 8 + [_c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                                                  _c.c_size_t, _c.c_void_p]
+lib.athd_head_cond.restype = _c.c_int
+lib.athd_head_cond_backward.argtypes = [_c.c_void_p] + [_c.c_void_p] * 8 + [_c.c_int64, _c.c_int64] + [_c.c_void_p] * 7 + [
+    _c.c_void_p, _c.c_size_t, _c.c_void_p]
+lib.athd_head_cond_backward.restype = _c.c_int
 lib.athd_num_windows.argtypes = [_c.c_int64, _c.c_int64, _c.c_int64]
 lib.athd_num_windows.restype = _c.c_int64
 lib.athd_overlap_add.argtypes = [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int64,
@@ -154,7 +162,8 @@ EXPORTED = ["athd_version", "athd_create", "athd_set_weight", "athd_num_required
             "athd_text_destroy", "athd_embed_compare_scratch_bytes", "athd_embed_compare",
             "athd_loss_grad_scratch_bytes", "athd_loss_grad_coef", "athd_loss_grad_apply",
             "athd_gather_train_segments", "athd_encode_workspace_bytes", "athd_encode", "athd_pack_spectrum",
-            "athd_head_output_workspace_bytes", "athd_head_output", "athd_head_output_backward"]
+            "athd_head_output_workspace_bytes", "athd_head_output", "athd_head_output_backward",
+            "athd_head_cond_workspace_bytes", "athd_head_cond", "athd_head_cond_backward"]
 
 F32, BF16 = 0, 1
 
@@ -228,6 +237,23 @@ class Context:
     def head_output_backward(self, grad_out_ptr, logits_ptr, spec_ptr, B, T, grad_logits_ptr, stream_ptr):
         self._check(lib.athd_head_output_backward(self.h, grad_out_ptr, logits_ptr, spec_ptr, B, T, grad_logits_ptr,
                                                   stream_ptr), "athd_head_output_backward")
+
+    @staticmethod
+    def head_cond_workspace_bytes(B: int, N: int) -> int:
+        return int(lib.athd_head_cond_workspace_bytes(B, N))
+
+    def head_cond(self, x_ptr, a_ptr, w0_ptr, b0_ptr, w2_ptr, b2_ptr, gamma_ptr, beta_ptr, B, N, y_ptr, ws_ptr, ws_bytes,
+                  stream_ptr):
+        self._check(lib.athd_head_cond(self.h, x_ptr, a_ptr, w0_ptr, b0_ptr, w2_ptr, b2_ptr, gamma_ptr, beta_ptr, B, N,
+                                       y_ptr, ws_ptr, ws_bytes, stream_ptr), "athd_head_cond")
+
+    def head_cond_backward(self, grad_y_ptr, x_ptr, a_ptr, w0_ptr, b0_ptr, w2_ptr, b2_ptr, gamma_ptr, B, N, grad_w0_ptr,
+                           grad_b0_ptr, grad_w2_ptr, grad_b2_ptr, grad_gamma_ptr, grad_beta_ptr, grad_a_ptr, ws_ptr,
+                           ws_bytes, stream_ptr):
+        self._check(lib.athd_head_cond_backward(self.h, grad_y_ptr, x_ptr, a_ptr, w0_ptr, b0_ptr, w2_ptr, b2_ptr,
+                                                gamma_ptr, B, N, grad_w0_ptr, grad_b0_ptr, grad_w2_ptr, grad_b2_ptr,
+                                                grad_gamma_ptr, grad_beta_ptr, grad_a_ptr, ws_ptr, ws_bytes, stream_ptr),
+                    "athd_head_cond_backward")
 
     def profile_start(self, kernel: str | None = None):
         """Time every launch of `kernel` (rocprof symbol short form; None = all kernels) with HIP events."""

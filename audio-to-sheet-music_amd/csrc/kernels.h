@@ -319,4 +319,19 @@ int pack_spec_launch(const float* z, int64_t B, int64_t Tspec, float* specT, hip
 int head_grad_launch(const float* g, const float* fo, const float* specT, int64_t B, int Tspec, int64_t T,
                      const float2* tw, const float* win, const float* win2, float* gfo, hipStream_t s);
 
+// head_cond.hip: head training's text-conditioning stage (include/athd.h), all f32.
+// x, y, gy [B][384][N]; a [B][384]; w0, w2 [384][384] row-major [out][in]; ws: head_cond_ws_floats(B, N) floats, 16-byte
+// aligned (0 = shape out of range: B in [1, 65535], N in [1, HEAD_COND_MAX_N]).  Every output element is written; fixed
+// summation order, no atomics.  Each returns -1 for a bad argument (nothing launched) or a HIP error.
+constexpr int HEAD_COND_C = 384, HEAD_COND_TN = 64, HEAD_COND_SLICES = 14;
+constexpr int64_t HEAD_COND_MAX_N = 1 << 20;
+int64_t head_cond_ws_floats(int64_t B, int64_t N);
+int head_cond_fwd_launch(const float* x, const float* a, const float* w0, const float* b0, const float* w2,
+                         const float* b2, const float* gamma, const float* beta, int64_t B, int64_t N, float* y,
+                         hipStream_t s);
+int head_cond_bwd_launch(const float* gy, const float* x, const float* a, const float* w0, const float* b0,
+                         const float* w2, const float* b2, const float* gamma, int64_t B, int64_t N, float* gw0,
+                         float* gb0, float* gw2, float* gb2, float* ggamma, float* gbeta, float* ga, float* ws,
+                         hipStream_t s);
+
 }  // namespace athd

@@ -151,6 +151,46 @@ int athd_head_output(athd_ctx* ctx, const float* logits, const float* spec, cons
 int athd_head_output_backward(athd_ctx* ctx, const float* grad_out, const float* logits, const float* spec, int64_t B,
                               int64_t T, float* grad_logits, void* stream);
 
+/* ---- Head training's text-conditioning stage (ATHTDemucs_v2.py:21-58) in both directions, from raw f32 weights ----
+ * The cross-attention has ONE key, so its output is one vector per item, a (B, 384) = out_proj(in_proj_v(v_proj(text))),
+ * which the caller computes (three tiny matrix-vector products, differentiable where it computes them).  The rest of the
+ * stage, per item b on its (384, N) channel-first slab X exactly as athd_encode exports x_enc / xt_enc (the frequency
+ * branch's (B, 384, 8, Ts) is the same memory as (B, 384, 8 Ts)), columns = tokens:
+ *   U = X + a_b;  V = U + W2 gelu_erf(W0 U + b0) + b2;  Y = gamma (V - mu) r + beta, (mu, r) the mean and
+ *   1 / sqrt(var + 1e-5) of each column over the 384 channels (out_mlp.0 / out_mlp.2 / norm_out; weights (384, 384)
+ *   row-major [out][in] as torch keeps them).  y (B, 384, N), channel-first like x.
+ * All pointers are device f32; the weights are read as they are at the time the kernels run (nothing is packed, nothing
+ * is cached across calls: a training step may change them between calls).  The context is taken for its device only: the
+ * arithmetic is f32 (v_mfma_f32_16x16x4_f32 and IEEE erf / exp / sqrt / division) in both dtype modes, bit-identical
+ * between them.
+ *
+ * athd_head_cond_backward: grad_y (B, 384, N) = dL/dy with the x, a and weights of the forward -> grad_w0, grad_w2
+ * (384, 384), grad_b0, grad_b2, grad_gamma, grad_beta (384) and grad_a (B, 384) = dL/da; x gets no gradient (it comes
+ * from the frozen half).  The forward is recomputed from x; nothing is saved between the two calls.  Every output element
+ * is written, none is accumulated into and none is read.  Sums over tokens run in a fixed order (per 64-token tile, then
+ * tiles in order per item, then items in order; the weight gradients as a split-K GEMM over a fixed 14 slices summed in
+ * slice order) and there are no atomics: the same bits on every run and under graph replay.
+ *
+ * ws: device, 16-byte aligned, not initialised by the caller, athd_head_cond_workspace_bytes(B, N) bytes (about
+ * 4 x B x ceil(N / 64) x 64 x 384 floats: the tiles of U, G, dV and dH for the weight-gradient GEMM).  Only the backward
+ * uses it; athd_head_cond takes the arguments for symmetry, ignores them and accepts NULL / 0.  w0, w2, grad_w0 and
+ * grad_w2 must be 16-byte aligned; x, y and grad_y may have any 4-byte alignment and any N (16-byte loads are used when
+ * N is a multiple of 4 and the base is 16-byte aligned, scalar ones otherwise).
+ *
+ * Both enqueue on the caller's stream, do not synchronise the host and create no HIP object, so they can be
+ * graph-captured from the first call.  ATHD_ESTATE before athd_finalize; ATHD_EINVAL for a null pointer, B outside
+ * [1, 65535], N < 1 or N > 1048576, a misaligned weight or workspace; ATHD_EWORKSPACE below
+ * athd_head_cond_workspace_bytes (which is 0 for shapes out of range).  Checked in that order before anything is read
+ * or written. */
+size_t athd_head_cond_workspace_bytes(int64_t B, int64_t N);
+int athd_head_cond(athd_ctx* ctx, const float* x, const float* a, const float* w0, const float* b0, const float* w2,
+                   const float* b2, const float* gamma, const float* beta, int64_t B, int64_t N, float* y, void* ws,
+                   size_t ws_bytes, void* stream);
+int athd_head_cond_backward(athd_ctx* ctx, const float* grad_y, const float* x, const float* a, const float* w0,
+                            const float* b0, const float* w2, const float* b2, const float* gamma, int64_t B, int64_t N,
+                            float* grad_w0, float* grad_b0, float* grad_w2, float* grad_b2, float* grad_gamma,
+                            float* grad_beta, float* grad_a, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Track level: the window loop of test_inference.py:92-141 and sdr_loss (src/loss.py:9-30) ----
  * Windows: start_k = k*hop with hop = chunk_len - overlap, for k = 0 .. athd_num_windows()-1 (while start < length),
  * end_k = min(start_k + chunk_len, length).  Window k is faded by torchaudio Fade(fade_in = k ? overlap : 0,
