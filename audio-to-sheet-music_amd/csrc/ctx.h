@@ -1,13 +1,13 @@
-// Private: athd context (packed device weights) shared by athd_api.cpp and forward.cpp.
+// Private: athd context: the packed device weights, their allocation and upload (host repacks: pack.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
 
 #include "gemm.h"
+#include "pack.h"
 #include "prof.h"
 
 namespace athd {
@@ -51,106 +51,27 @@ struct TLayerW {
     float *n1w, *n1b, *n2w, *n2b, *n3w = nullptr, *n3b = nullptr, *now, *nob, *g1, *g2;
 };
 
+// One decoder level.  pack_decoders builds what the level's route reads (forward_dec.cpp), the rest stays null:
+//   level | freq                                  | time
+//   0     | pair                                  | pair
+//   1     | taps, bias                            | pair
+//   2     | quad, + ct4w / ct4b in bf16 mode      | the same
+//   3     | nothing (folded: athd_ctx::flast)     | nothing (folded: athd_ctx::tlast)
 struct DecW {
     int cin = 0, cout = 0;
     GemmW pair[2];          // ConvTranspose residue pairs {0,1} (taps u-1,u) and {2,3} (taps u,u+1), N = 2*cout
-    GemmW quad;             // levels 2: all four residues in one GEMM, rows [rho * cout + co], K = [row u-1 | u | u+1]
-    uint16_t* ct4w = nullptr;   // level 2, bf16 mode: [rho * cout + co][2 cin] = the residue pair's two rows (convt4.hip)
+    GemmW quad;             // all four residues in one GEMM, rows [rho * cout + co], K = [row u-1 | u | u+1]
+    uint16_t* ct4w = nullptr;   // [rho * cout + co][2 cin] = the residue pair's two rows (convt4.hip)
     float* ct4b = nullptr;      //   and the bias [cout]
-    GemmW taps;             // freq level 1 only: every tap as its own column block, N = 8*cout, K = cin (fdec_lr.hip)
-    float* bias = nullptr;  // freq level 1 only: ConvT bias [cout]
-    float *gnw = nullptr, *gnb = nullptr;
+    GemmW taps;             // every tap as its own column block, N = 8*cout, K = cin (fdec_lr.hip)
+    float* bias = nullptr;  // with taps: ConvT bias [cout]
+    float *gnw = nullptr, *gnb = nullptr;      // levels 0-2
 };
 
-}  // namespace athd
-
-namespace athd {
-inline uint16_t host_f2bf(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-// Moments of a 1x1 conv W [N][H] (row-major), b [N] for GroupNorm statistics from its input alone:
-// [G = W^T W (H x H) | v = W^T b (H) | ws = W^T 1 (H) | sum b | sum b^2], accumulated in fp64; round_bf16: from the
-// bf16-rounded weights the MFMA kernels multiply with
-inline std::vector<float> conv1x1_moments(const std::vector<float>& w, const std::vector<float>& b, int N, int H,
-                                          bool round_bf16) {
-    std::vector<double> g((size_t)H * H + 2 * H + 2, 0.0);
-    auto wv = [&](int n, int j) -> double {
-        const float x = w[(size_t)n * H + j];
-        if (!round_bf16) return x;
-        const uint32_t u = (uint32_t)host_f2bf(x) << 16;
-        float r;
-        std::memcpy(&r, &u, 4);
-        return r;
-    };
-    for (int n = 0; n < N; ++n) {
-        const double bn = b[n];
-        for (int j = 0; j < H; ++j) {
-            const double wj = wv(n, j);
-            for (int k = 0; k < H; ++k) g[(size_t)j * H + k] += wj * wv(n, k);
-            g[(size_t)H * H + j] += bn * wj;
-            g[(size_t)H * H + H + j] += wj;
-        }
-        g[(size_t)H * H + 2 * H] += bn;
-        g[(size_t)H * H + 2 * H + 1] += bn * bn;
-    }
-    return std::vector<float>(g.begin(), g.end());
-}
-// K order of the rewrite weights that the fused DConv apply multiplies (dconv.hip dconv_apply_kernel<C, NW, true>,
-// C = 48, 96): K slot 32 ks + 8 g + i holds channel 32 ks + 4 g + i (i < 4) or 32 ks + 16 + 4 g + (i - 4), the order in
-// which a lane holds its row's updated channels.  Slots whose channel is >= C are zero.
-inline int dconv_rewrite_perm(int k) {
-    const int ks = k / 32, g = (k % 32) / 8, i = k % 8;
-    return 32 * ks + (i < 4 ? 4 * g + i : 16 + 4 * g + (i - 4));
-}
-// The last decoder level folded with its 1x1 output projection (dec_last.hip's header), in double.  w: ConvT weight
-// [48][4][8], b: its bias [4], P: freq_out / time_out weight [2][4], pb: its bias [2]; br 0 = freq, 1 = time.
-//   freq: [Am | A0 | Ap] (3 x [2][48]: P W7 / 2, P (W3 + W4) / 2, P W0 / 2), P b + pb (2), 0.1 P (8)
-//   time: Q_k = P W_k (8 x [2][48]), P b (2), pb (2), 0.1 P (8)
-inline std::vector<float> dec_last_fold(const std::vector<float>& w, const std::vector<float>& b,
-                                        const std::vector<float>& P, const std::vector<float>& pb, int br) {
-    const int cin = 48, co = 4;
-    auto pw = [&](int j, int ci, int k) {     // (P W_k)[j][ci]
-        double a = 0.0;
-        for (int cc = 0; cc < co; ++cc) a += (double)P[j * co + cc] * w[((size_t)ci * co + cc) * 8 + k];
-        return a;
-    };
-    double pbias[2];
-    for (int j = 0; j < 2; ++j) {
-        pbias[j] = 0.0;
-        for (int cc = 0; cc < co; ++cc) pbias[j] += (double)P[j * co + cc] * b[cc];
-    }
-    std::vector<float> f;
-    if (br == 0) {
-        for (int m = 0; m < 3; ++m)
-            for (int j = 0; j < 2; ++j)
-                for (int ci = 0; ci < cin; ++ci)
-                    f.push_back((float)(0.5 * (m == 0 ? pw(j, ci, 7) : m == 1 ? pw(j, ci, 3) + pw(j, ci, 4) : pw(j, ci, 0))));
-        for (int j = 0; j < 2; ++j) f.push_back((float)(pbias[j] + pb[j]));
-    } else {
-        for (int k = 0; k < 8; ++k)
-            for (int j = 0; j < 2; ++j)
-                for (int ci = 0; ci < cin; ++ci) f.push_back((float)pw(j, ci, k));
-        for (int j = 0; j < 2; ++j) f.push_back((float)pbias[j]);
-        for (int j = 0; j < 2; ++j) f.push_back(pb[j]);
-    }
-    for (int j = 0; j < 2; ++j)
-        for (int cc = 0; cc < co; ++cc) f.push_back((float)(0.1 * P[j * co + cc]));
-    return f;
-}
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t rup(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 constexpr int ENC_CH[4] = {48, 96, 192, 384};
 constexpr int DEC_CH[5] = {384, 192, 96, 48, 4};
-// ConvTranspose (k8 s4 p2) residue classes: output row 4u+rho = taps in rows u+in_off, u+in_off+1 with kernel
-// indices {k0, k1}
-constexpr int RES_OFF[4] = {-1, -1, 0, 0};
-constexpr int RES_K0[4] = {6, 7, 4, 5};
-constexpr int RES_K1[4] = {2, 3, 0, 1};
-
 // Bump allocator over the caller's workspace (or sizing pass when base == nullptr).
 struct Arena {
     char* base = nullptr;
@@ -192,7 +113,6 @@ struct athd_ctx {
     float *ta_maT, *ta_ma, *ta_mcT, *ta_mc, *ta_m2b, *ta_nw, *ta_nb;
     GemmW mlp0, mlp2;
     DecW fdec[4], tdec[4];
-    float *fout_w, *fout_b, *tout_w, *tout_b;
     float* flast = nullptr;          // folded last freq level + freq_out (dec_last.hip)
     float* tlast = nullptr;          // folded last time level + time_out
     float2* tw = nullptr;
@@ -247,48 +167,31 @@ struct athd_ctx {
         g.bias = bias.empty() ? nullptr : up_f32(bias);
         return g;
     }
-    // conv weight [Cout][Cin][taps] -> [Cout][tap*Cin + ci]
+    // conv weight [Cout][Cin][taps] tap-major; glu: rows and bias in GLU pair order
     GemmW conv_gemm(const std::string& wk, const std::string& bk, int cout, int cin, int taps, bool glu = false) {
-        const auto& w = W(wk).v;
-        std::vector<float> p((size_t)cout * taps * cin);
-        for (int co = 0; co < cout; ++co)
-            for (int ci = 0; ci < cin; ++ci)
-                for (int t = 0; t < taps; ++t) p[((size_t)co * taps + t) * cin + ci] = w[((size_t)co * cin + ci) * taps + t];
-        std::vector<float> b = W(bk).v;
-        if (glu) {   // pair order: per 32 packed rows [a(16q..16q+15) | gate(C+16q..)]
-            std::vector<float> q(p.size());
-            const int K = taps * cin;
-            for (int pr = 0; pr < cout; ++pr)
-                std::memcpy(&q[(size_t)pr * K], &p[(size_t)glu_src(pr, cout) * K], K * 4);
-            p.swap(q);
-            b = glu_order(b);
-        }
-        return up_gemm(p, cout, taps * cin, b);
+        const int K = taps * cin;
+        const std::vector<float> p = conv_tap_major(W(wk).v, cout, cin, taps);
+        const std::vector<float>& b = W(bk).v;
+        return glu ? up_gemm(glu_order(p, K), cout, K, glu_order(b)) : up_gemm(p, cout, K, b);
     }
-    static int glu_src(int pr, int n) {
-        const int C = n / 2, qq = pr / 32, s = pr % 32;
-        return s < 16 ? 16 * qq + s : C + 16 * qq + (s - 16);
-    }
-    static std::vector<float> glu_order(const std::vector<float>& v) {
-        std::vector<float> o(v.size());
-        for (size_t i = 0; i < v.size(); ++i) o[i] = v[glu_src((int)i, (int)v.size())];
-        return o;
-    }
-    // rows [row0, row0 + rows) of a [N][K] linear layer; the first `scaled_rows` of them (weights and bias) times
-    // `scale` (the attention query prescale, see ATTN_Q_PRESCALE)
+    // pack.h lin_rows of a [N][K] linear layer (scale: the attention query prescale, see ATTN_Q_PRESCALE)
     GemmW lin_gemm(const std::string& wk, const std::string& bk, int row0 = 0, int rows = -1, int scaled_rows = 0,
                    float scale = 1.f) {
         const HostT& w = W(wk);
-        int N = (int)w.shape[0], K = (int)w.shape[1];
+        const int N = (int)w.shape[0], K = (int)w.shape[1];
         if (rows < 0) rows = N - row0;
-        std::vector<float> p(w.v.begin() + (size_t)row0 * K, w.v.begin() + (size_t)(row0 + rows) * K);
-        const auto& bb = W(bk).v;
-        std::vector<float> b(bb.begin() + row0, bb.begin() + row0 + rows);
-        for (int n = 0; n < scaled_rows && n < rows; ++n) {
-            for (int k = 0; k < K; ++k) p[(size_t)n * K + k] *= scale;
-            b[n] *= scale;
-        }
-        return up_gemm(p, rows, K, b);
+        const PackedRows p = lin_rows(w.v, W(bk).v, K, row0, rows, scaled_rows, scale);
+        return up_gemm(p.w, rows, K, p.bias);
     }
 };
+
+// pack.cpp: the state-dict keys with their shapes, and athd_finalize's packing of c.host, one function per stage
+namespace athd {
+const std::vector<std::pair<std::string, std::vector<int64_t>>>& required_keys();
+void pack_encoders(athd_ctx& c);
+void pack_transformer(athd_ctx& c);
+void pack_text_attn(athd_ctx& c);
+void pack_decoders(athd_ctx& c);
+void pack_tables(athd_ctx& c);       // FFT twiddles and windows
+}  // namespace athd
 

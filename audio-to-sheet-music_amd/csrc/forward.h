@@ -1,5 +1,6 @@
 // Internal to the forward orchestration (forward*.cpp): shapes and workspace (Dims, Bufs), the run state (Run), the
-// stream plan, the runtime switches, the GemmDesc builders and the stage prototypes.
+// stream plan, the runtime switches, the GemmDesc builders and the stage prototypes.  The tensors' layout in HBM:
+// DESIGN.md §2.
 #pragma once
 #include <hip/hip_runtime.h>
 

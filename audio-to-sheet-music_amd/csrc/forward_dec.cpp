@@ -37,11 +37,11 @@ void conv_t(Run& r, const DecW& w, const void* A, int a_bf16, int nb, int H_in, 
         r.gemm(g, "convt.quad");
         return;
     }
+    // the pair GEMMs store all rows, and only the levels routed here have pair weights (ctx.h DecW)
+    if (!w.pair[0].w || !w.pair[1].w || keep >= 0) { r.check(-2, "convt: no packed route"); return; }
     for (int pi = 0; pi < 2; ++pi) {
         GemmDesc g = residues(w.pair[pi], 2, pi == 0 ? -1 : 0);
-        if (keep < 0) { g.o_off = 2 * pi; g.store_mask = 3; }
-        else if (pi == 0) { g.o_off = 0; g.hi_row_off = 0; g.store_mask = 2; }   // residue 1 -> slot 2u
-        else { g.o_off = 1; g.store_mask = 1; }                                   // residue 2 -> slot 2u+1
+        g.o_off = 2 * pi; g.store_mask = 3;
         r.gemm(g, pi == 0 ? "convt.pair01" : "convt.pair23");
     }
 }

@@ -151,7 +151,7 @@ struct FencRowDesc {
     const uint16_t* w1[2] = {nullptr, nullptr}; int w1_ld = 0;                    // 1x1 [2C][C/8] GLU-interleaved
     const float* b1[2] = {nullptr, nullptr};
     const float* g2w[2] = {nullptr, nullptr}; const float* g2b[2] = {nullptr, nullptr};   // packed order
-    const float* gram[2] = {nullptr, nullptr};    // 1x1 moments (ctx.h conv1x1_moments, bf16-rounded weights)
+    const float* gram[2] = {nullptr, nullptr};    // 1x1 moments (pack.h conv1x1_moments, bf16-rounded weights)
     const float* scale[2] = {nullptr, nullptr};
     const uint16_t* wr = nullptr; int wr_ld = 0; const float* br = nullptr;      // rewrite [2C][C] GLU-interleaved
     const float* row_add = nullptr;    // level 0: freq embedding [Fout][C]
@@ -231,14 +231,14 @@ struct DconvDesc {
     int w3_kp = 0, w1_kp = 0;
     const float *b3 = nullptr, *g1w = nullptr, *g1b = nullptr, *scale = nullptr;
     const float *b1 = nullptr, *g2w = nullptr, *g2b = nullptr;   // in the row order of the 1x1 weights in use
-    const float* gram = nullptr;                    // ctx.h conv1x1_moments of the 1x1 weights in use
+    const float* gram = nullptr;                    // pack.h conv1x1_moments of the 1x1 weights in use
 };
 // dconv_small.hip: the layer as three VALU kernels (C = 48, 96; M = nb L); -2 if the shape is not covered
 int dconv_small_launch(const DconvDesc& d, hipStream_t s);
 // dconv.hip: the layer as three weights-resident passes (bf16 mode); -1 before any launch unless the predicate holds.
 // conv3 + GroupNorm statistics of h; hb = bf16(GELU(GN(h))) + the 1x1's statistics from d.gram (M = nb L); the 1x1
 // apply, with rw (C = 48, 96) followed in registers by the level's rewrite out = GLU(Wr x + br) instead of the store to
-// x (rw.w: [2C][kp] GLU-interleaved rows in the K order of ctx.h dconv_rewrite_perm)
+// x (rw.w: [2C][kp] GLU-interleaved rows in the K order of pack.h dconv_rewrite_perm)
 struct DcRewrite {
     const uint16_t* w;
     int kp;

@@ -9,6 +9,7 @@
 #include "ctx.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "pack.h"
 #include "text_tower.h"
 
 namespace athd {   // norm.hip, dec_last.hip, fdec1f.hip: the tuning constants next to their launchers
@@ -246,8 +247,8 @@ void kt_dconv_plan(int64_t mode, int64_t C, int64_t nb, int64_t L, int64_t rewri
     out[0] = p.ok; out[1] = p.valu; out[2] = p.conv3_mfma; out[3] = p.norm; out[4] = p.apply_mfma; out[5] = p.rewrite;
 }
 
-// ---- the host-side packers of ctx.h (no GPU) ----
-int64_t kt_glu_src(int64_t pr, int64_t n) { return athd_ctx::glu_src((int)pr, (int)n); }
+// ---- the host-side packers of pack.h (no GPU) ----
+int64_t kt_glu_src(int64_t pr, int64_t n) { return glu_src((int)pr, (int)n); }
 int64_t kt_rewrite_perm(int64_t k) { return dconv_rewrite_perm((int)k); }
 int64_t kt_host_f2bf(int64_t f32_bits) {
     const uint32_t u = (uint32_t)f32_bits;
@@ -338,12 +339,28 @@ int64_t kt_dm_run() { return dec_merge_run(); }
 int64_t kt_merge_maxp() { return dec_merge_maxp(); }
 int64_t kt_g_wb() { return fdec1_gram_wb(); }
 int64_t kt_fdec1_gram_blocks() { return fdec1_gram_blocks(); }      // (queries the current device's CU count)
-// ctx.h dec_last_fold (host): w [48][4][8], b [4], P [2][4], pb [2] -> out (br 0: 298 floats, br 1: 780)
+// pack.h dec_last_fold (host): w [48][4][8], b [4], P [2][4], pb [2] -> out (br 0: 298 floats, br 1: 780)
 int64_t kt_dec_last_fold(const float* w, const float* b, const float* P, const float* pb, int64_t br, float* out) {
     const std::vector<float> f = dec_last_fold(std::vector<float>(w, w + 48 * 4 * 8), std::vector<float>(b, b + 4),
                                                std::vector<float>(P, P + 8), std::vector<float>(pb, pb + 2), (int)br);
     if (out) memcpy(out, f.data(), f.size() * sizeof(float));
     return (int64_t)f.size();
+}
+// pack.h ConvT residue rows (host) of w [cin][cout][8], b [cout].  form 0: convt_pair(pi) -> rows f32 [2 cout][2 cin],
+// bias [2 cout]; 1: convt_quad -> rows f32 [4 cout][3 cin], bias [4 cout]; 2: convt4_rows -> rows bf16 [4 cout][2 cin],
+// no bias.  Returns the number of row elements written.
+int64_t kt_convt_rows(const float* w, const float* b, int64_t cin, int64_t cout, int64_t form, int64_t pi, void* rows,
+                      float* bias) {
+    const std::vector<float> wv(w, w + cin * cout * 8), bv(b, b + cout);
+    if (form == 2) {
+        const std::vector<uint16_t> q = convt4_rows(wv, bv, (int)cin, (int)cout);
+        memcpy(rows, q.data(), q.size() * sizeof(uint16_t));
+        return (int64_t)q.size();
+    }
+    const PackedRows p = form == 0 ? convt_pair(wv, bv, (int)cin, (int)cout, (int)pi) : convt_quad(wv, bv, (int)cin, (int)cout);
+    memcpy(rows, p.w.data(), p.w.size() * sizeof(float));
+    memcpy(bias, p.bias.data(), p.bias.size() * sizeof(float));
+    return (int64_t)p.w.size();
 }
 
 int kt_gn_apply(float* x, int64_t nb, int64_t N, int64_t C, const double* stats, const float* w, const float* b,

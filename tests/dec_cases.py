@@ -140,7 +140,7 @@ def last_ref(c, x=None, d_in=None, mut=None):
 
 
 def last_emulate(c, fold, x=None):
-    """the folded form of dec_last.hip's header in float32 from the product's fold (ctx.h dec_last_fold)"""
+    """the folded form of dec_last.hip's header in float32 from the product's fold (pack.h dec_last_fold)"""
     br, NI, P, H = c["br"], c["NI"], c["P"], c["H"]
     x = (c["x"] if x is None else x).astype(F)
     fold = np.asarray(fold, dtype=F)

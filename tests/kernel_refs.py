@@ -37,7 +37,7 @@ SURVEY.md Appendix A: conv3 -> GroupNorm(1) -> GELU -> 1x1 -> GroupNorm(1) -> GL
   z = (v - m) r w + b,  |dz| <= |w| r (d + dm + |v - m| drr) + 4e (|c| + |b| + |m| r |w|) with c = (v - m) r w: the
   LayerNorm rule above with the statistics' own bound as input instead of mean(d), rms(d).  Statistics a kernel reads
   from memory (fp64 {sum, sumsq} written by an earlier pass) are exact inputs: dm = drr = 0.
-* Moment-form statistics of y = W x + b over its N outputs (ctx.h conv1x1_moments: G = W^T W, v = W^T b, ws = W^T 1):
+* Moment-form statistics of y = W x + b over its N outputs (pack.h conv1x1_moments: G = W^T W, v = W^T b, ws = W^T 1):
   sum_n y = sum b + ws.x,  sum_n y^2 = sum b^2 + 2 v.x + x^T G x.  The reference evaluates y itself in f64 from the
   row x the kernel stored (bf16, checked separately: no rounding-tie ambiguity).  The kernel evaluates the form in f32:
   H^2 + H products and as many additions for the quadratic term, 2H for each linear term, 4 to combine, every one
@@ -236,7 +236,7 @@ def attn_emulate_bf16(q, k, v, scale, kt=64):
 
 
 # ------------------------------------------------------------------------------------------------ ConvTranspose
-RES_OFF = (-1, -1, 0, 0)      # csrc/ctx.h: output row 4u + rho reads input rows u + RES_OFF[rho] and the next one
+RES_OFF = (-1, -1, 0, 0)      # csrc/pack.h: output row 4u + rho reads input rows u + RES_OFF[rho] and the next one
 RES_K0 = (6, 7, 4, 5)         #             with kernel taps RES_K0[rho] and RES_K1[rho]
 RES_K1 = (2, 3, 0, 1)
 
@@ -476,7 +476,7 @@ def gemm_ref(g, mode, tap_shift=0, pad_neighbour=False, stats_shift=False):
 
 # ------------------------------------------------------------------------------------------------ DConv packers
 def glu_src(pr, n):
-    """ctx.h: packed row pr of a GLU-interleaved [n = 2C] layer reads natural row glu_src: per 32 packed rows
+    """pack.h: packed row pr of a GLU-interleaved [n = 2C] layer reads natural row glu_src: per 32 packed rows
     [a(16q .. 16q+15) | gate(C + 16q .. C + 16q + 15)]"""
     C, q, s = n // 2, pr // 32, pr % 32
     return 16 * q + s if s < 16 else C + 16 * q + (s - 16)
@@ -489,7 +489,7 @@ def glu_order(v):
 
 
 def rewrite_perm(k):
-    """K slot k of the fused rewrite's weights holds channel rewrite_perm(k) (kernels.h DcRewrite, ctx.h
+    """K slot k of the fused rewrite's weights holds channel rewrite_perm(k) (kernels.h DcRewrite, pack.h
     dconv_rewrite_perm): slot 32 ks + 8 g + i <- channel 32 ks + 4 g + i (i < 4) or 32 ks + 16 + 4 g + (i - 4)"""
     ks, g, i = k // 32, (k % 32) // 8, k % 8
     return 32 * ks + (4 * g + i if i < 4 else 16 + 4 * g + (i - 4))
@@ -525,7 +525,7 @@ def rewrite_pack(wr):
 
 def conv1x1_moments(w, b, round_bf16):
     """[G = W^T W (H x H) | v = W^T b | ws = W^T 1 | sum b | sum b^2] of W [N][H], b [N] as float32, accumulated in
-    float64 row by row (ctx.h conv1x1_moments); round_bf16: from the bf16-rounded weights"""
+    float64 row by row (pack.h conv1x1_moments); round_bf16: from the bf16-rounded weights"""
     w = np.asarray(w, dtype=np.float32)
     w = bf16_round(w) if round_bf16 else w.astype(np.float64)
     b = np.asarray(b, dtype=np.float32).astype(np.float64)

@@ -117,6 +117,8 @@ lib.kt_fdec1_gram_floats.restype = _I
 lib.kt_fdec1_gram_floats.argtypes = [_I, _I]
 lib.kt_dec_last_fold.restype = _I
 lib.kt_dec_last_fold.argtypes = [_P, _P, _P, _P, _I, _P]
+lib.kt_convt_rows.restype = _I
+lib.kt_convt_rows.argtypes = [_P, _P, _I, _I, _I, _I, _P, _P]
 # ---- the spectral front and back end, tconv0, text_vec, the position tables (tests/test_gpu_spectral.py) ----
 ST_FIELDS = "wav nb T Tspec tw tw64 win specT stats pp_L pp_left pp_ext_left pp_Lx".split()
 IS_FIELDS = "fo NI Tspec P T spec tw tw64 win win2 xt2 tnorm out part".split()
@@ -154,8 +156,26 @@ LRSTEP = np.dtype([("lz", "<f4"), ("lk", "<f4"), ("lj", "<f4"), ("zk", "<u4"), (
                    ("pad", "<u4", (2,))])
 
 
+CONVT_PAIR, CONVT_QUAD, CONVT4 = 0, 1, 2
+
+
+def convt_rows(w, b, form, pi=0):
+    """pack.h ConvT residue rows of a weight [cin][cout][8], bias [cout] -> (rows, bias): CONVT_PAIR (pair pi) float32
+    [2 cout][2 cin], CONVT_QUAD float32 [4 cout][3 cin], CONVT4 bf16 bits [4 cout][2 cin] with bias None"""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    cin, cout = w.shape[:2]
+    assert w.shape == (cin, cout, 8) and b.shape == (cout,)
+    nres, nrows = ((2, 2), (4, 3), (4, 2))[form]
+    rows = np.zeros((nres * cout, nrows * cin), dtype=np.uint16 if form == CONVT4 else np.float32)
+    bias = np.zeros(nres * cout, dtype=np.float32)
+    n = lib.kt_convt_rows(w.ctypes.data, b.ctypes.data, cin, cout, form, pi, rows.ctypes.data, bias.ctypes.data)
+    assert n == rows.size
+    return rows, (None if form == CONVT4 else bias)
+
+
 def dec_last_fold(w, b, P, pb, br):
-    """ctx.h dec_last_fold: ConvT weight [48][4][8], bias [4], projection [2][4], bias [2], branch -> float32 fold"""
+    """pack.h dec_last_fold: ConvT weight [48][4][8], bias [4], projection [2][4], bias [2], branch -> float32 fold"""
     a = [np.ascontiguousarray(v, dtype=np.float32) for v in (w, b, P, pb)]
     assert a[0].shape == (48, 4, 8) and a[1].shape == (4,) and a[2].shape == (2, 4) and a[3].shape == (2,)
     n = lib.kt_dec_last_fold(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, br, None)
@@ -165,7 +185,7 @@ def dec_last_fold(w, b, P, pb, br):
 
 
 def conv1x1_moments(w, b, round_bf16):
-    """ctx.h conv1x1_moments of W [N][H], b [N] -> float32 [H*H + 2H + 2]"""
+    """pack.h conv1x1_moments of W [N][H], b [N] -> float32 [H*H + 2H + 2]"""
     w = np.ascontiguousarray(w, dtype=np.float32)
     b = np.ascontiguousarray(b, dtype=np.float32)
     N, H = w.shape

@@ -1,6 +1,6 @@
 """CPU checks of the decoder references of tests/kernel_refs.py (lin_index_ref, resize_h_ref, dec_merge_ref, dec_last_ref,
 fdec_lr_ref) and of the host code behind tests/test_gpu_dec.py: the struct sizes of libathd_ktest.so, the last level's
-fold (ctx.h dec_last_fold) and the host-only shape predicates.  No GPU.
+fold (pack.h dec_last_fold) and the host-only shape predicates.  No GPU.
 
 * Every reference equals the same chain of torch.nn.functional (conv_transpose2d / 1d, interpolate, group_norm, gelu) in
   float64: the resize to 1e-6 relative (float32 lambda against float64 lambda), the rest to 1e-12.
@@ -89,6 +89,63 @@ def test_dec_last_fold(ktl, br):
         assert abs(got[(3 * 2 + 1) * 48 + 7] - Q(3, 1, 7)) < 1e-6                 # Q_3[1][7]
         assert np.allclose(got[768:770], P @ b, atol=1e-6) and (got[770:772] == pb).all()
         assert np.allclose(got[772:], (0.1 * P).ravel(), atol=1e-7)
+
+
+def _bf16_bits(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).bfloat16().view(torch.int16).numpy().view(np.uint16)
+
+
+# (cin, cout, H): a first row with no u - 1, a last row with no u + 1, an interior row, the product's channel counts
+@pytest.mark.parametrize("cin,cout,H", [(1, 1, 1), (3, 2, 2), (3, 2, 5), (96, 48, 3)])
+def test_convt_rows(ktl, cin, cout, H):
+    """the packed ConvTranspose (k8, s4, p2) residue rows of pack.h, applied to their window of input rows (rows outside
+    [0, H) are zero), reproduce torch's conv_transpose1d in float64 at output rows 4u + rho to 1e-12 relative (only the
+    summation order differs): the two pairs (residues {2pi, 2pi+1} over rows u + RES_OFF[2pi], +1), the quad (all four
+    over u-1, u, u+1) and the convt4 form (residue rho over its own rows u + RES_OFF[rho], +1; its rows are bf16, so the
+    convolution it reproduces is the one with the bf16-rounded weights, and its bias is the layer's own).  Every packed
+    entry is bit-equal to a source weight (convt4: to its bf16 rounding) or exactly +0, and the convt4 rows are bit-equal
+    to the product's host_f2bf of the quad's columns of those rows."""
+    rng = np.random.default_rng(1000 * cin + 10 * cout + H)
+    w = rng.standard_normal((cin, cout, 8)).astype(np.float32)
+    b = rng.standard_normal(cout).astype(np.float32)
+    x = rng.standard_normal((H, cin))
+    wb = torch.from_numpy(w).bfloat16().double().numpy()          # the weights the convt4 rows hold
+
+    def conv(wt):       # [4 H][cout]
+        y = Fn.conv_transpose1d(torch.from_numpy(x.T[None]), torch.from_numpy(wt).double(), torch.from_numpy(b).double(),
+                                stride=4, padding=2)
+        assert y.shape == (1, cout, 4 * H)
+        return y[0].T.numpy()
+
+    ref, ref_b = conv(w), conv(wb)
+    xp = np.zeros((H + 2, cin))
+    xp[1:H + 1] = x                                               # input row r at xp[r + 1]
+
+    def apply(rows, bias, row_lo, nrows):     # [H][rows]: the rows times the window u + row_lo .. + nrows - 1
+        win = np.concatenate([xp[1 + row_lo + j:1 + row_lo + j + H] for j in range(nrows)], axis=1)
+        return win @ rows.astype(np.float64).T + bias.astype(np.float64)
+
+    wbits = np.append(w.view(np.uint32).ravel(), np.uint32(0))
+    for pi in range(2):
+        rows, bias = ktl.convt_rows(w, b, ktl.CONVT_PAIR, pi)
+        assert np.isin(rows.view(np.uint32), wbits).all() and (bias == np.tile(b, 2)).all()
+        got = apply(rows, bias, kr.RES_OFF[2 * pi], 2)
+        for h in range(2):
+            assert _rel(got[:, h * cout:(h + 1) * cout], ref[2 * pi + h::4]) <= 1e-12, (pi, h)
+    quad, qbias = ktl.convt_rows(w, b, ktl.CONVT_QUAD)
+    assert np.isin(quad.view(np.uint32), wbits).all() and (qbias == np.tile(b, 4)).all()
+    got = apply(quad, qbias, -1, 3)
+    for rho in range(4):
+        assert _rel(got[:, rho * cout:(rho + 1) * cout], ref[rho::4]) <= 1e-12, rho
+    ct4, none = ktl.convt_rows(w, b, ktl.CONVT4)
+    assert none is None and np.isin(ct4, np.append(_bf16_bits(w).ravel(), np.uint16(0))).all()
+    ct4f = (ct4.astype(np.uint32) << 16).view(np.float32)
+    for rho in range(4):
+        sl = slice(rho * cout, (rho + 1) * cout)
+        qwin = quad[sl, (kr.RES_OFF[rho] + 1) * cin:(kr.RES_OFF[rho] + 3) * cin]
+        f2bf = np.array([ktl.lib.kt_host_f2bf(int(v)) for v in qwin.view(np.uint32).ravel()], dtype=np.uint16)
+        assert (ct4[sl].ravel() == f2bf).all(), rho
+        assert _rel(apply(ct4f[sl], b, kr.RES_OFF[rho], 2), ref_b[rho::4]) <= 1e-12, rho
 
 
 def _dl(ktl, **kw):

@@ -1,7 +1,7 @@
 """Kernel-level parity of the decoder kernels against the float64 references and derived tolerances of
 tests/kernel_refs.py, through libathd_ktest.so: the step table and the two passes of the low-rank level 1 (csrc/fdec_lr.hip),
 the decoder merges (dec_merge_* of csrc/norm.hip) and the folded last level of both branches with and without the fused
-level-2 merge (csrc/dec_last.hip; the fold itself is ctx.h dec_last_fold, so fold and kernel are checked together).
+level-2 merge (csrc/dec_last.hip; the fold itself is pack.h dec_last_fold, so fold and kernel are checked together).
 
 The rules of tests/test_gpu_kernels.py and tests/test_gpu_dconv.py hold: guard bands on every operand, sentinels in every
 output, neighbouring items and segments scaled by different powers of two (tests/dec_cases.py), |got - R| <= tol for every
