@@ -6,7 +6,8 @@ the HTDemucs encoders, the cross-transformer and CLAP run frozen under `no_grad`
 differentiable by autograd on any device and dtype; `HeadTrainer` joins the two behind the `model(mixture, prompts)`
 call that `athd.train.train_epoch` expects.  The model's backward stays torch's, except for the output
 stage (mask, iSTFT, denormalisation), which `native_output=True` runs natively in both directions (`NativeOutputStage`),
-and the text-conditioning stage, which `native_cond=True` does (`NativeCondStage`).
+the text-conditioning stage, which `native_cond=True` does (`NativeCondStage`), and the two decoders, which
+`native_decoders=True` does level by level (`NativeDecoderLevel`).
 
 `TrainableHead.state_dict()` has exactly the 50 reference key names and shapes outside `htdemucs.` / `clap.`
 (`athd.weights.hot_path_spec`), so a trained head drops into a reference-format checkpoint and loads straight back into
@@ -126,6 +127,64 @@ class _Decoder(nn.Module):
                 x = x + 0.1 * self._resize(skips[i][:, :x.shape[1]], x.shape[2])
         return x
 
+    def forward_native(self, x: torch.Tensor, skips: List[torch.Tensor], targets: List[int], nctx) -> torch.Tensor:
+        """`forward` through `NativeDecoderLevel`, level by level on the channel-first layout as it is (no permute): x
+        (B, 384, F, Ts) or (B, 384, L) float32; float32 whatever autocast says"""
+        with torch.autocast(device_type=x.device.type, enabled=False):
+            x = x.float().contiguous()
+            for i, layer in enumerate(self.layers):
+                conv, norm = layer[0], (layer[1] if len(layer) > 1 else None)
+                co = conv.out_channels
+                target = targets[i] if i < len(targets) else 4 * x.shape[2]
+                skip = skips[i][:, :co].float().contiguous() if i < len(skips) else None
+                x = NativeDecoderLevel.apply(x, conv.weight, conv.bias, norm.weight if norm is not None else None,
+                                             norm.bias if norm is not None else None, skip, i, int(target), nctx)
+        return x
+
+
+class NativeDecoderLevel(torch.autograd.Function):
+    """One decoder level in libathd.so, both directions (`athd_head_dec_level`, `athd_head_dec_level_backward`,
+    include/athd.h): `x (B, Ci, M[, inner])` contiguous float32, the level's ConvTranspose weight and bias, its GroupNorm
+    weight and bias (None on the last level) and the encoder skip `(B, Co, S[, inner])` (or None) -> `y (B, Co, Lt[,
+    inner])` = resize(gelu(norm(convT(x)))) + 0.1 resize(skip).  The skip gets no gradient (it comes from the frozen
+    half).  The backward recomputes the level from `x`: besides `x`, the parameters and the two statistics per item
+    nothing is saved, none of the level's (Co, 4 M, inner) tensors; the workspace lives only inside each call."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, skip, level, target, nctx):
+        B, _, M = x.shape[:3]
+        inner = x.shape[3] if x.dim() == 4 else 1
+        params = [p.detach().float().contiguous() if p is not None else None for p in (w, b, gamma, beta)]
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        S = skip.shape[2] if skip is not None else 0
+        y = torch.empty((B, w.shape[1], target) + tuple(x.shape[3:]), dtype=torch.float32, device=x.device)
+        stats = torch.empty((B, 2), dtype=torch.float32, device=x.device)
+        ws = torch.empty(max(nctx.head_dec_workspace_bytes(level, B, M, inner, target), 16), dtype=torch.uint8,
+                         device=x.device)
+        nctx.head_dec_level(level, x.data_ptr(), *[ptr(p) for p in params], ptr(skip), B, M, inner, S, target,
+                            y.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(),
+                            torch.cuda.current_stream(x.device).cuda_stream)
+        ctx.save_for_backward(x, stats, *[p for p in params if p is not None])
+        ctx.nctx, ctx.args = nctx, (level, B, M, inner, target)
+        ctx.dtypes = [p.dtype if p is not None else None for p in (w, b, gamma, beta)]
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, stats, w, b, *gn = ctx.saved_tensors
+        gamma, beta = gn if gn else (None, None)
+        level, B, M, inner, target = ctx.args
+        g = g.float().contiguous()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        grads = [torch.empty_like(p) if p is not None else None for p in (x, w, b, gamma, beta)]
+        ws = torch.empty(max(ctx.nctx.head_dec_workspace_bytes(level, B, M, inner, target), 16), dtype=torch.uint8,
+                         device=g.device)
+        ctx.nctx.head_dec_level_backward(level, g.data_ptr(), x.data_ptr(), w.data_ptr(), b.data_ptr(), ptr(gamma),
+                                         ptr(beta), stats.data_ptr(), B, M, inner, target, *[ptr(t) for t in grads],
+                                         ws.data_ptr(), ws.numel(), torch.cuda.current_stream(g.device).cuda_stream)
+        return (grads[0],) + tuple(t.to(d) if t is not None else None for t, d in zip(grads[1:], ctx.dtypes)) + (
+            None, None, None, None)
+
 
 class _DeadParams(torch.autograd.Function):
     """`a` unchanged, with the dead parameters attached to the graph: the backward hands each of them an exact zero
@@ -225,10 +284,14 @@ class TrainableHead(nn.Module):
     `native_cond=True` does the same for the first stage, the text conditioning (`NativeCondStage`: the residual MLP and
     LayerNorm on the features' channel-first layout, no permute, and their gradients; the attention vector per item stays
     torch's).  Same requirements (bound model, float32 parameters on its GPU) plus contiguous float32 features on that
-    GPU, as `encode` returns them; it raises otherwise.  Under autocast it computes and returns float32.  The two options
-    are independent and compose."""
+    GPU, as `encode` returns them; it raises otherwise.  Under autocast it computes and returns float32.
 
-    def __init__(self, native_output: bool = False, native_cond: bool = False):
+    `native_decoders=True` does the same for both decoders (`NativeDecoderLevel`, four levels each, on the conditioned
+    features' channel-first layout as it is; `freq_out` / `time_out` stay torch's).  Same requirements and refusals as
+    `native_cond` (bound model, float32 parameters on its GPU, float32 features and skips on that GPU); float32 under
+    autocast.  The three options are independent and compose."""
+
+    def __init__(self, native_output: bool = False, native_cond: bool = False, native_decoders: bool = False):
         super().__init__()
         self.text_attn = _TextAttention()
         self.freq_decoder = _Decoder(True)
@@ -237,6 +300,7 @@ class TrainableHead(nn.Module):
         self.time_out = nn.Conv1d(DEC_CH[-1], 2, 1)
         self.native_output = bool(native_output)
         self.native_cond = bool(native_cond)
+        self.native_decoders = bool(native_decoders)
         object.__setattr__(self, "_native_model", None)      # a plain attribute, not a submodule
         object.__setattr__(self, "_spec_cache", None)        # (weakref to z, its version, packed spectrum)
 
@@ -291,6 +355,25 @@ class TrainableHead(nn.Module):
                                    f"...) on the model's device, got {t.dtype} {tuple(t.shape)} on {t.device}")
         return self.text_attn.forward_native(f.x_enc, f.xt_enc, text_emb.to(p.device), model._ensure_ctx())
 
+    def _native_decoder_stage(self, f: EncodedFeatures, x_cond: torch.Tensor, xt_cond: torch.Tensor):
+        model, p = self._native_model, self.freq_decoder.layers[0][0].weight
+        if model is None:
+            raise RuntimeError("native_decoders=True needs the native model: call head.bind(model) (HeadTrainer does)")
+        if p.dtype != torch.float32 or p.device.type != "cuda" or p.device != model.device:
+            raise RuntimeError(f"native_decoders=True needs float32 parameters on the model's device {model.device}, got "
+                               f"{p.dtype} on {p.device}; leave the option off for the torch decoders")
+        feats = [("x_enc", f.x_enc), ("xt_enc", f.xt_enc)]
+        feats += [(f"skips[{i}]", t) for i, t in enumerate(f.skips)] + [(f"skips_t[{i}]", t)
+                                                                        for i, t in enumerate(f.skips_t)]
+        for name, t in feats:
+            if t.dtype != torch.float32 or t.device != p.device or t.dim() < 3 or t.numel() == 0:
+                raise RuntimeError(f"native_decoders=True needs the features' {name} as float32 (B, C, ...) on the "
+                                   f"model's device, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        nctx = model._ensure_ctx()
+        xd = self.freq_decoder.forward_native(x_cond, list(f.skips[::-1]), list(f.lengths[::-1]), nctx)
+        xtd = self.time_decoder.forward_native(xt_cond, list(f.skips_t[::-1]), list(f.lengths_t[::-1]), nctx)
+        return xd, xtd
+
     @classmethod
     def from_model(cls, model) -> "TrainableHead":
         """The 50 head tensors of a loaded `AudioTextHTDemucs` (float32, on the CPU; move it with `.to`)"""
@@ -324,8 +407,11 @@ class TrainableHead(nn.Module):
             x_cond, xt_cond = self.text_attn(cast(f.x_enc), cast(f.xt_enc), cast(text_emb))
         # frequency branch: logits on a (Ts, Ts) grid (the reference resizes the FREQUENCY axis to `lengths`, the frame
         # counts)
-        xd = self.freq_decoder(x_cond, [cast(s) for s in f.skips[::-1]], list(f.lengths[::-1]))
-        xtd = self.time_decoder(xt_cond, [cast(s) for s in f.skips_t[::-1]], list(f.lengths_t[::-1]))
+        if self.native_decoders:
+            xd, xtd = self._native_decoder_stage(f, x_cond, xt_cond)
+        else:
+            xd = self.freq_decoder(x_cond, [cast(s) for s in f.skips[::-1]], list(f.lengths[::-1]))
+            xtd = self.time_decoder(xt_cond, [cast(s) for s in f.skips_t[::-1]], list(f.lengths_t[::-1]))
         return x_cond, xt_cond, self.freq_out(xd), self.time_out(xtd)
 
     def forward(self, f: EncodedFeatures, text_emb: torch.Tensor) -> torch.Tensor:
@@ -355,18 +441,20 @@ class HeadTrainer(nn.Module):
     model is a plain attribute (not a submodule): `parameters()`, `train()` and `eval()` are the head's."""
 
     def __init__(self, model, head: Optional[TrainableHead] = None, native_output: bool = False,
-                 native_cond: bool = False):
+                 native_cond: bool = False, native_decoders: bool = False):
         super().__init__()
         object.__setattr__(self, "model", model)
         if head is None:
             if model.device is None:
                 model.to("cuda")
             head = TrainableHead.from_model(model).to(model.device)
-        # native_output / native_cond: the head's last / first stage and its gradient in libathd.so (TrainableHead); a
-        # head that was built with an option keeps it.  Only such a head holds a reference to the native model.
+        # native_output / native_cond / native_decoders: the head's last / first / middle stage and its gradient in
+        # libathd.so (TrainableHead); a head that was built with an option keeps it.  Only such a head holds a reference
+        # to the native model.
         head.native_output = bool(native_output or head.native_output)
         head.native_cond = bool(native_cond or head.native_cond)
-        if head.native_output or head.native_cond:
+        head.native_decoders = bool(native_decoders or head.native_decoders)
+        if head.native_output or head.native_cond or head.native_decoders:
             head.bind(model)
         self.head = head
 

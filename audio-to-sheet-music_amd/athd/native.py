@@ -63,6 +63,14 @@ lib.athd_head_cond.restype = _c.c_int
 lib.athd_head_cond_backward.argtypes = [_c.c_void_p] + [_c.c_void_p] * 8 + [_c.c_int64, _c.c_int64] + [_c.c_void_p] * 7 + [
     _c.c_void_p, _c.c_size_t, _c.c_void_p]
 lib.athd_head_cond_backward.restype = _c.c_int
+lib.athd_head_dec_workspace_bytes.argtypes = [_c.c_int] + [_c.c_int64] * 4
+lib.athd_head_dec_workspace_bytes.restype = _c.c_size_t
+lib.athd_head_dec_level.argtypes = [_c.c_void_p, _c.c_int] + [_c.c_void_p] * 6 + [_c.c_int64] * 5 + [
+    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]
+lib.athd_head_dec_level.restype = _c.c_int
+lib.athd_head_dec_level_backward.argtypes = [_c.c_void_p, _c.c_int] + [_c.c_void_p] * 7 + [_c.c_int64] * 4 + [
+    _c.c_void_p] * 5 + [_c.c_void_p, _c.c_size_t, _c.c_void_p]
+lib.athd_head_dec_level_backward.restype = _c.c_int
 lib.athd_num_windows.argtypes = [_c.c_int64, _c.c_int64, _c.c_int64]
 lib.athd_num_windows.restype = _c.c_int64
 lib.athd_overlap_add.argtypes = [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int64,
@@ -163,7 +171,8 @@ EXPORTED = ["athd_version", "athd_create", "athd_set_weight", "athd_num_required
             "athd_loss_grad_scratch_bytes", "athd_loss_grad_coef", "athd_loss_grad_apply",
             "athd_gather_train_segments", "athd_encode_workspace_bytes", "athd_encode", "athd_pack_spectrum",
             "athd_head_output_workspace_bytes", "athd_head_output", "athd_head_output_backward",
-            "athd_head_cond_workspace_bytes", "athd_head_cond", "athd_head_cond_backward"]
+            "athd_head_cond_workspace_bytes", "athd_head_cond", "athd_head_cond_backward",
+            "athd_head_dec_workspace_bytes", "athd_head_dec_level", "athd_head_dec_level_backward"]
 
 F32, BF16 = 0, 1
 
@@ -254,6 +263,24 @@ class Context:
                                                 gamma_ptr, B, N, grad_w0_ptr, grad_b0_ptr, grad_w2_ptr, grad_b2_ptr,
                                                 grad_gamma_ptr, grad_beta_ptr, grad_a_ptr, ws_ptr, ws_bytes, stream_ptr),
                     "athd_head_cond_backward")
+
+    @staticmethod
+    def head_dec_workspace_bytes(level: int, B: int, M: int, inner: int, Lt: int) -> int:
+        return int(lib.athd_head_dec_workspace_bytes(level, B, M, inner, Lt))
+
+    def head_dec_level(self, level, x_ptr, w_ptr, bias_ptr, gamma_ptr, beta_ptr, skip_ptr, B, M, inner, S, Lt, y_ptr,
+                       stats_ptr, ws_ptr, ws_bytes, stream_ptr):
+        self._check(lib.athd_head_dec_level(self.h, level, x_ptr, w_ptr, bias_ptr, gamma_ptr, beta_ptr, skip_ptr, B, M,
+                                            inner, S, Lt, y_ptr, stats_ptr, ws_ptr, ws_bytes, stream_ptr),
+                    "athd_head_dec_level")
+
+    def head_dec_level_backward(self, level, grad_y_ptr, x_ptr, w_ptr, bias_ptr, gamma_ptr, beta_ptr, stats_ptr, B, M,
+                                inner, Lt, grad_x_ptr, grad_w_ptr, grad_bias_ptr, grad_gamma_ptr, grad_beta_ptr, ws_ptr,
+                                ws_bytes, stream_ptr):
+        self._check(lib.athd_head_dec_level_backward(self.h, level, grad_y_ptr, x_ptr, w_ptr, bias_ptr, gamma_ptr,
+                                                     beta_ptr, stats_ptr, B, M, inner, Lt, grad_x_ptr, grad_w_ptr,
+                                                     grad_bias_ptr, grad_gamma_ptr, grad_beta_ptr, ws_ptr, ws_bytes,
+                                                     stream_ptr), "athd_head_dec_level_backward")
 
     def profile_start(self, kernel: str | None = None):
         """Time every launch of `kernel` (rocprof symbol short form; None = all kernels) with HIP events."""

@@ -334,4 +334,20 @@ int head_cond_bwd_launch(const float* gy, const float* x, const float* a, const 
                          float* gb0, float* gw2, float* gb2, float* ggamma, float* gbeta, float* ga, float* ws,
                          hipStream_t s);
 
+// head_dec.hip: one level of head training's decoders (include/athd.h), all f32.  level 0..3 = (Ci, Co) (384, 192),
+// (192, 96), (96, 48), (48, 4); x [B][Ci][M][inner], w [Ci][Co][8], skip [B][Co][S][inner] or nullptr with S = 0,
+// y, gy [B][Co][Lt][inner], stats [B][2] = {mu, r} (levels 0..2; gamma, beta, stats and their gradients may be nullptr at
+// level 3).  ws: head_dec_ws_floats() floats, 16-byte aligned (0 = shape out of range).  Every output element is written;
+// fixed summation order, no atomics.  Each returns -1 for a bad argument (nothing launched) or a HIP error.
+constexpr int64_t HEAD_DEC_MAX_M = 1 << 20, HEAD_DEC_MAX_INNER = 4096, HEAD_DEC_MAX_LT = 1 << 22;
+constexpr int64_t HEAD_DEC_MAX_TOKENS = 1 << 26;        // M inner; Lt inner and S inner up to four times that
+int64_t head_dec_ws_floats(int level, int64_t B, int64_t M, int64_t inner, int64_t Lt);
+int head_dec_fwd_launch(int level, const float* x, const float* w, const float* bias, const float* gamma,
+                        const float* beta, const float* skip, int64_t B, int64_t M, int64_t inner, int64_t S, int64_t Lt,
+                        float* y, float* stats, float* ws, hipStream_t s);
+int head_dec_bwd_launch(int level, const float* gy, const float* x, const float* w, const float* bias,
+                        const float* gamma, const float* beta, const float* stats, int64_t B, int64_t M, int64_t inner,
+                        int64_t Lt, float* gx, float* gw, float* gb, float* ggamma, float* gbeta, float* ws,
+                        hipStream_t s);
+
 }  // namespace athd

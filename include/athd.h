@@ -191,6 +191,62 @@ int athd_head_cond_backward(athd_ctx* ctx, const float* grad_y, const float* x, 
                             float* grad_w0, float* grad_b0, float* grad_w2, float* grad_b2, float* grad_gamma,
                             float* grad_beta, float* grad_a, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Head training's decoder levels (ATHTDemucs_v2.py:61-139) in both directions, from raw f32 weights ----
+ * Both decoders are four levels of one operation along one axis of a channel-first slab: the frequency decoder on
+ * (B, C, F, Ts) with inner = Ts contiguous columns per position, the time decoder on (B, C, L) with inner = 1.  Level l
+ * in 0..3 has (Ci, Co) = (384, 192), (192, 96), (96, 48), (48, 4); levels 0..2 have GroupNorm(1) + GELU.  Per item, with
+ * x (Ci, M, inner), W (Ci, Co, 8) as torch keeps a ConvTranspose weight ((Ci, Co, 8, 1) is the same memory) and every
+ * index along the position axis:
+ *   c[co, o] = b[co] + sum_ci W[ci, co, k1] x[ci, m1] + W[ci, co, k1 + 4] x[ci, m1 - 1],  k1 = (o + 2) mod 4,
+ *              m1 = (o + 2) div 4, terms with m outside [0, M) dropped; c is (Co, 4 M, inner)
+ *   h = gelu_erf(gamma_co (c - mu) r + beta_co), (mu, r) the mean and 1 / sqrt(var + 1e-5) of c over the whole item
+ *       (biased variance); level 3: h = c
+ *   y = resize(h) + 0.1 resize(skip): the position axis to Lt by torch's linear rule with align_corners = False, in
+ *       its f32 arithmetic (src = max(0, (o + 0.5) in / Lt - 0.5), i0 = floor(src), i1 = min(i0 + 1, in - 1), weight
+ *       src - i0; the identity when Lt == in), for any ratio: up, down or near 1.  skip (B, Co, S, inner) gets no
+ *       gradient (it comes from the frozen half); skip == NULL with S == 0 means no skip.
+ * y (B, Co, Lt, inner); stats (B, 2) = {mu, r} per item, what the backward needs beside x.
+ *
+ * athd_head_dec_level_backward: grad_y (B, Co, Lt, inner) with the x, parameters and stats of the forward -> grad_x
+ * (B, Ci, M, inner), grad_w (Ci, Co, 8), grad_bias (Co), grad_gamma, grad_beta (Co).  c is recomputed from x; the
+ * adjoint of the resize is a gather per source position (no scatter), then gelu', the GroupNorm backward
+ * dc = r (D - mean D - ch mean(D ch)), D = gamma dz, ch = (c - mu) r, and the two GEMMs.  At level 3 gamma, beta, stats,
+ * grad_gamma and grad_beta are ignored and may be NULL.
+ *
+ * All pointers are device f32; the weights are read raw at the time the kernels run (nothing is packed, nothing is
+ * cached across calls).  The context is taken for its device only: the three GEMMs of a level run on
+ * v_mfma_f32_16x16x4_f32 with IEEE erf / exp / sqrt / division in both dtype modes, bit-identical between them (level 3's
+ * data gradient, 32 products per element, is a plain kernel that sums in double and rounds once).  x, y,
+ * skip and grad_y may have any 4-byte alignment, inner and Lt any value in range (all operand loads are scalar); w and
+ * grad_w must be 16-byte aligned, as torch allocates them.
+ *
+ * Determinism: no atomics.  Every output element is written exactly once, none is accumulated into or read.  Sums over
+ * positions are taken per block of 1024 positions of a channel (8192 elements for the statistics) by a fixed tree,
+ * then over the blocks in order, then over the items in order; the mean is taken first and the variance from the centred
+ * values; grad_w is a split-K GEMM over the tokens of all items in a fixed number of slices per level (8, 16, 32, 64)
+ * summed in slice order.  The same bits on every run and under graph replay.
+ *
+ * ws: device, 16-byte aligned, not initialised by the caller, athd_head_dec_workspace_bytes() bytes, the same for both
+ * directions: with n = Co 4 M inner, q = ceil(4 M inner / 1024) and up4 rounding up to a multiple of 4, in floats
+ *   2 up4(B n)  (c and one gradient tensor of its size)  + up4(B ceil(n / 8192)) + 2 up4(2 B)
+ *   + up4(2 B Co q) + up4(B Co q) + up4(2 B Co) + up4(slices Ci Co 8);  it does not depend on Lt.
+ *
+ * Both enqueue on the caller's stream, do not synchronise the host and create no HIP object, so they can be
+ * graph-captured from the first call.  ATHD_ESTATE before athd_finalize; ATHD_EINVAL for a null required pointer, level
+ * outside 0..3, B outside [1, 65535], M outside [1, 1048576], inner outside [1, 4096], Lt outside [1, 4194304],
+ * M inner > 67108864 or Lt inner > 268435456 (2048 frames need M <= 524288 and Lt <= 2097152 in the time decoder and
+ * M, inner, Lt <= 2048 in the frequency decoder), a skip without S or S without a skip (S within Lt's limits), a
+ * misaligned weight or workspace; ATHD_EWORKSPACE for no workspace or one below athd_head_dec_workspace_bytes (which is
+ * 0 for shapes out of range).  Checked in that order before anything is read or written. */
+size_t athd_head_dec_workspace_bytes(int level, int64_t B, int64_t M, int64_t inner, int64_t Lt);
+int athd_head_dec_level(athd_ctx* ctx, int level, const float* x, const float* w, const float* bias, const float* gamma,
+                        const float* beta, const float* skip, int64_t B, int64_t M, int64_t inner, int64_t S, int64_t Lt,
+                        float* y, float* stats, void* ws, size_t ws_bytes, void* stream);
+int athd_head_dec_level_backward(athd_ctx* ctx, int level, const float* grad_y, const float* x, const float* w,
+                                 const float* bias, const float* gamma, const float* beta, const float* stats, int64_t B,
+                                 int64_t M, int64_t inner, int64_t Lt, float* grad_x, float* grad_w, float* grad_bias,
+                                 float* grad_gamma, float* grad_beta, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Track level: the window loop of test_inference.py:92-141 and sdr_loss (src/loss.py:9-30) ----
  * Windows: start_k = k*hop with hop = chunk_len - overlap, for k = 0 .. athd_num_windows()-1 (while start < length),
  * end_k = min(start_k + chunk_len, length).  Window k is faded by torchaudio Fade(fade_in = k ? overlap : 0,
