@@ -72,15 +72,17 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t rup(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 constexpr int ENC_CH[4] = {48, 96, 192, 384};
 constexpr int DEC_CH[5] = {384, 192, 96, 48, 4};
-// Bump allocator over the caller's workspace (or sizing pass when base == nullptr).
+// Bump allocator over the caller's workspace (or sizing pass when base == nullptr).  gap: unused bytes after every
+// buffer, 0 in the product; the workspace tests set it (athd_ctx::arena_gap) and check that nothing writes there.
 struct Arena {
     char* base = nullptr;
     size_t off = 0;
+    size_t gap = 0;
     template <typename T>
     T* take(int64_t n) {
         size_t bytes = (size_t)rup((int64_t)(n * (int64_t)sizeof(T)), 256);
         T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += bytes;
+        off += bytes + gap;
         return p;
     }
 };
@@ -96,6 +98,7 @@ struct athd_ctx {
     int mode = 1;
     // (segment, prompt) items per decode chunk (athd_set_decode_items): the decoder's workspace scales with it
     int64_t decode_items = 64;
+    size_t arena_gap = 0;            // Arena::gap of the forward's workspace plan (tests only: ktest.cpp kt_set_arena_gap)
     bool finalized = false;
     std::string err;
     std::map<std::string, HostT> host;

@@ -13,10 +13,10 @@ int forward_impl(athd_ctx* c, const float* wav, int64_t B, int64_t T, const floa
     if (T > (int64_t)1 << 26) return c->fail(ATHD_EINVAL, "segment too long");
     const Dims d = make_dims(c, B, T, P);
     Bufs b;
-    Arena sz;
+    Arena sz{nullptr, 0, c->arena_gap};
     const size_t need = plan(sz, d, b, c->mode == 1);
     if (!ws || ws_bytes < need) return c->fail(ATHD_EWORKSPACE, "workspace too small: need " + std::to_string(need));
-    Arena ar{(char*)ws};
+    Arena ar{(char*)ws, 0, c->arena_gap};
     plan(ar, d, b, c->mode == 1);
     if (hipSetDevice(c->device) != hipSuccess) return c->fail(ATHD_EHIP, "hipSetDevice failed");
     Run r(c, (hipStream_t)stream, b.stats);   // reads the runtime switches and sets up the stream plan
@@ -35,7 +35,7 @@ int forward_impl(athd_ctx* c, const float* wav, int64_t B, int64_t T, const floa
         decode_chunk(r, d, b, s0, bc, text, per_item, out, (ch & 1) && b.FO2 ? b.FO2 : b.FO);
     }
     if (r.ok()) r.sp.final_join();   // the last chunk's iSTFT (second stream) joins the caller's stream
-    if (d.chunks == 1) dump_all(d, b, r.xt2, r.s);
+    if (d.chunks == 1) dump_all(d, b, r.xt2, c->arena_gap, r.s);
     if (r.err) return c->fail(ATHD_EHIP, "launch failed in " + r.what + " (code " + std::to_string(r.err) + ")");
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return c->fail(ATHD_EHIP, std::string("HIP error: ") + hipGetErrorString(e));
@@ -51,7 +51,7 @@ extern "C" {
 size_t athd_workspace_bytes(athd_ctx* c, int64_t B, int64_t T, int P) {
     if (!c || B <= 0 || T <= 0 || P <= 0) return 0;
     Bufs b;
-    Arena a;
+    Arena a{nullptr, 0, c->arena_gap};
     return plan(a, make_dims(c, B, T, P), b, c->mode == 1);
 }
 

@@ -190,7 +190,7 @@ inline GemmDesc lin(const GemmW& w, const void* A, int a_bf16, int64_t nb, int64
 // ---- stages ----
 Dims make_dims(const athd_ctx* c, int64_t B, int64_t T, int P);                  // forward_plan.cpp
 size_t plan(Arena& ar, const Dims& d, Bufs& b, bool actbf);
-void dump_all(const Dims& d, const Bufs& b, const float* xt2, hipStream_t s);
+void dump_all(const Dims& d, const Bufs& b, const float* xt2, size_t gap, hipStream_t s);
 void encode(Run& r, const Dims& d, const Bufs& b, const float* wav);             // forward_enc.cpp
 void transformer(Run& r, const Dims& d, const Bufs& b);                          // forward_xf.cpp
 // one decode chunk of Bc segments from segment s0 (sets r.xt2)                  // forward_dec.cpp

@@ -49,10 +49,10 @@ int encode_impl(athd_ctx* c, const float* wav, int64_t B, int64_t T, const athd_
     if (T > (int64_t)1 << 26) return c->fail(ATHD_EINVAL, "segment too long");
     const Dims d = make_dims(c, B, T, 1);
     Bufs b;
-    Arena sz;
+    Arena sz{nullptr, 0, c->arena_gap};
     const size_t need = plan(sz, d, b, c->mode == 1);
     if (!ws || ws_bytes < need) return c->fail(ATHD_EWORKSPACE, "workspace too small: need " + std::to_string(need));
-    Arena ar{(char*)ws};
+    Arena ar{(char*)ws, 0, c->arena_gap};
     plan(ar, d, b, c->mode == 1);
     if (hipSetDevice(c->device) != hipSuccess) return c->fail(ATHD_EHIP, "hipSetDevice failed");
     Run r(c, (hipStream_t)stream, b.stats);

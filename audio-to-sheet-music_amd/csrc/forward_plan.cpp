@@ -120,7 +120,7 @@ static bool dump_dev(const char* dir, const std::string& name, const void* p, si
 
 // Debug aid: ATHD_DUMP=<dir> makes the forward synchronise at the end and write the main intermediates of the
 // first decode chunk as raw little-endian arrays (<dir>/<name>.f32 / .f64) plus <dir>/index.txt with shapes.
-void dump_all(const Dims& d, const Bufs& b, const float* xt2, hipStream_t s) {
+void dump_all(const Dims& d, const Bufs& b, const float* xt2, size_t gap, hipStream_t s) {
     const char* dir = std::getenv("ATHD_DUMP");
     if (!dir || !*dir) return;
     if (hipStreamSynchronize(s) != hipSuccess) return;
@@ -144,13 +144,13 @@ void dump_all(const Dims& d, const Bufs& b, const float* xt2, hipStream_t s) {
             dump_dev(dir, "saved_t" + si + ".bf16", b.saved_t[i], (size_t)nt * 2);
         }
     }
-    // the decoder's scratch buffers as raw bytes (<name>.raw; sizes from the arena order in plan())
+    // the decoder's scratch buffers as raw bytes (<name>.raw; sizes from the arena order in plan(), less Arena::gap)
     struct Rw { const char* name; const void* p; const void* end; };
     const Rw rws[] = {{"G", b.G, b.D}, {"D", b.D, b.Gt}, {"Gt", b.Gt, b.Dt}, {"Dt", b.Dt, b.S}, {"S", b.S, b.Z},
                       {"Z", b.Z, b.Zs}, {"Zs", b.Zs, b.FO}, {"stats", b.stats, b.specT}};
     for (const auto& e : rws)
-        if (e.p && e.end && e.end > e.p)
-            dump_dev(dir, std::string(e.name) + ".raw", e.p, (size_t)((const char*)e.end - (const char*)e.p));
+        if (e.p && e.end && (const char*)e.end > (const char*)e.p + gap)
+            dump_dev(dir, std::string(e.name) + ".raw", e.p, (size_t)((const char*)e.end - (const char*)e.p) - gap);
     FILE* fi = std::fopen((std::string(dir) + "/index.txt").c_str(), "w");
     for (const auto& e : es)
         if (dump_dev(dir, e.name + ".f32", e.p, (size_t)e.n * 4) && fi)

@@ -7,6 +7,7 @@
 
 #include "attn.h"
 #include "ctx.h"
+#include "forward.h"
 #include "gemm.h"
 #include "kernels.h"
 #include "pack.h"
@@ -479,6 +480,53 @@ int kt_ctx_tables(const athd_ctx* c, void** out) {
     if (!c || !c->finalized || !out) return -1;
     out[0] = c->tw; out[1] = c->tw64; out[2] = c->win; out[3] = c->win2;
     return 0;
+}
+
+// ---- the forward's workspace layout (forward_plan.cpp; tests/test_workspace_refs.py, tests/test_gpu_workspace.py) ----
+// unused bytes after every arena buffer of this context's forwards (Arena::gap)
+int kt_set_arena_gap(athd_ctx* c, int64_t bytes) {
+    if (!c || bytes < 0 || bytes % 256) return -1;
+    c->arena_gap = (size_t)bytes;
+    return 0;
+}
+
+// (offset, bytes) of every buffer of plan(), in plan()'s order (tests/ktest.py LAYOUT_NAMES), then the total at
+// out[2 * count]; returns the count, also when cap is too small (nothing is written then).  bytes is the rounded size
+// (next offset - this offset - gap); a slot that plan() leaves null has bytes == 0.  No context and no device: the
+// arena's base is an address that is only ever subtracted again, so the null slots are plan()'s own.
+int64_t kt_forward_layout(int bf16, int64_t decode_items, int64_t B, int64_t T, int P, int64_t gap, int64_t* out,
+                          int64_t cap) {
+    using namespace athd_fwd;
+    if (B <= 0 || T <= 0 || P <= 0 || gap < 0 || decode_items <= 0) return -1;
+    athd_ctx c;
+    c.decode_items = decode_items;
+    char* const base = reinterpret_cast<char*>((uintptr_t)1 << 40);
+    Arena ar{base, 0, (size_t)gap};
+    Bufs b{};
+    const size_t total = plan(ar, make_dims(&c, B, T, P), b, bf16 != 0);
+    const void* const slots[] = {
+        b.stats, b.specT, b.snorm, b.tnorm_div, b.tnorm_std,
+        b.saved[0], b.saved_t[0], b.saved[1], b.saved_t[1], b.saved[2], b.saved_t[2], b.saved[3], b.saved_t[3],
+        b.sk4, b.sk4t, b.ybuf_t, b.hbuf_t, b.hbuf_b_t, b.ybuf, b.hbuf, b.hbuf_b, b.X, b.XT,
+        b.H[0], b.H[1], b.H[2], b.H[3], b.QKV, b.O, b.F1, b.QKVt, b.Ot, b.F1t, b.pos2d, b.pos1d,
+        b.x_enc, b.xt_enc, b.x_enc_b, b.xt_enc_b, b.avec, b.tc0, b.tc2, b.Hm, b.Yb, b.Hmt, b.Ybt, b.x_cond, b.xt_cond,
+        b.G, b.D, b.Gt, b.Dt, b.S, b.Z, b.Zs, b.FO, b.FO2, b.ola_part, b.lrsteps, b.gram, b.gramq, b.skw[0], b.skw[1]};
+    const int64_t n = (int64_t)(sizeof(slots) / sizeof(slots[0]));
+    if (!out || cap < 2 * n + 1) return n;
+    int64_t next = (int64_t)total;
+    for (int64_t i = n - 1; i >= 0; --i) {
+        if (slots[i]) {
+            const int64_t off = (const char*)slots[i] - base;
+            out[2 * i] = off;
+            out[2 * i + 1] = next - off - gap;
+            next = off;
+        } else {
+            out[2 * i] = next;
+            out[2 * i + 1] = 0;
+        }
+    }
+    out[2 * n] = (int64_t)total;
+    return n;
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 A plain helper module of tests/test_gpu_kernels.py, tests/test_gpu_dconv.py, tests/test_gpu_dec.py and
 tests/test_gpu_spectral.py (tests/test_gpu_track_kernels.py uses its buffers, sync and report only); importing it needs the built libraries but no GPU (the host-side packers, folds, plans and shape
 predicates it exports are compared on the CPU, tests/test_dconv_refs.py, tests/test_dec_refs.py,
-tests/test_spectral_refs.py)."""
+tests/test_spectral_refs.py, and the forward's workspace layout, tests/test_workspace_refs.py)."""
 import ctypes
 import json
 import os
@@ -142,6 +142,33 @@ lib.kt_istft_part_floats.restype = _I
 lib.kt_istft_part_floats.argtypes = [_I, _I]
 lib.kt_pos2d.argtypes = [_P, _I, _I, _I, _P]
 lib.kt_pos1d.argtypes = [_P, _I, _I, _P]
+
+
+# ---- the forward's workspace layout (tests/test_workspace_refs.py, tests/test_gpu_workspace.py) ----
+lib.kt_set_arena_gap.argtypes = [_P, _I]
+lib.kt_forward_layout.restype = _I
+lib.kt_forward_layout.argtypes = [ctypes.c_int, _I, _I, _I, ctypes.c_int, _I, _P, _I]
+# the buffers of forward_plan.cpp plan(), in its order
+LAYOUT_NAMES = ("stats specT snorm tnorm_div tnorm_std saved0 saved_t0 saved1 saved_t1 saved2 saved_t2 saved3 saved_t3 "
+                "sk4 sk4t ybuf_t hbuf_t hbuf_b_t ybuf hbuf hbuf_b X XT H0 H1 H2 H3 QKV O F1 QKVt Ot F1t pos2d pos1d "
+                "x_enc xt_enc x_enc_b xt_enc_b avec tc0 tc2 Hm Yb Hmt Ybt x_cond xt_cond G D Gt Dt S Z Zs FO FO2 ola_part "
+                "lrsteps gram gramq skw0 skw1").split()
+DEFAULT_DECODE_ITEMS = 64             # ctx.h athd_ctx::decode_items
+
+
+def set_arena_gap(ctx, nbytes):
+    """unused bytes after every workspace buffer of this native.Context's forwards (0: the product's layout)"""
+    assert lib.kt_set_arena_gap(ctx.h, int(nbytes)) == 0
+
+
+def forward_layout(bf16, B, T, P=1, decode_items=DEFAULT_DECODE_ITEMS, gap=0):
+    """plan()'s workspace layout -> ([(name, offset, bytes)] in arena order, total bytes); bytes == 0: a null slot.
+    No context and no device.  (make_dims reads ATHD_DECODE_ITEMS: callers that pass decode_items keep it unset.)"""
+    cap = 2 * len(LAYOUT_NAMES) + 1
+    out = (ctypes.c_int64 * cap)()
+    n = lib.kt_forward_layout(int(bool(bf16)), decode_items, B, T, P, gap, out, cap)
+    assert n == len(LAYOUT_NAMES), (n, len(LAYOUT_NAMES))
+    return [(name, out[2 * i], out[2 * i + 1]) for i, name in enumerate(LAYOUT_NAMES)], out[2 * n]
 
 
 def stft_pad_plan(T, Tspec):
@@ -289,6 +316,7 @@ DCONV_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_dconv_report
 DEC_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_dec_report.json")
 SPECTRAL_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_spectral_report.json")
 TRACK_REPORT = os.path.join(os.path.dirname(REPORT), "kernel_parity_track_report.json")
+WORKSPACE_REPORT = os.path.join(os.path.dirname(REPORT), "workspace_report.json")
 _reports = {}
 
 
