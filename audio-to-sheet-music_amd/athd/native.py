@@ -71,6 +71,23 @@ lib.athd_head_dec_level.restype = _c.c_int
 lib.athd_head_dec_level_backward.argtypes = [_c.c_void_p, _c.c_int] + [_c.c_void_p] * 7 + [_c.c_int64] * 4 + [
     _c.c_void_p] * 5 + [_c.c_void_p, _c.c_size_t, _c.c_void_p]
 lib.athd_head_dec_level_backward.restype = _c.c_int
+class StepTensor(_c.Structure):
+    """athd_step_tensor (include/athd.h): one tensor of athd_head_step's host table"""
+    _fields_ = [("param", _c.c_void_p), ("grad", _c.c_void_p), ("exp_avg", _c.c_void_p), ("exp_avg_sq", _c.c_void_p),
+                ("n", _c.c_int64)]
+
+
+class StepHparams(_c.Structure):
+    """athd_step_hparams (include/athd.h); max_norm <= 0: no clipping"""
+    _fields_ = [(k, _c.c_double) for k in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm")]
+
+
+STEP_MAX_TENSORS = 64
+lib.athd_head_step_workspace_bytes.argtypes = [_c.POINTER(StepTensor), _c.c_int]
+lib.athd_head_step_workspace_bytes.restype = _c.c_size_t
+lib.athd_head_step.argtypes = [_c.POINTER(StepTensor), _c.c_int, _c.POINTER(StepHparams), _c.c_void_p, _c.c_void_p,
+                               _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]
+lib.athd_head_step.restype = _c.c_int
 lib.athd_num_windows.argtypes = [_c.c_int64, _c.c_int64, _c.c_int64]
 lib.athd_num_windows.restype = _c.c_int64
 lib.athd_overlap_add.argtypes = [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int64, _c.c_int64,
@@ -172,13 +189,33 @@ EXPORTED = ["athd_version", "athd_create", "athd_set_weight", "athd_num_required
             "athd_gather_train_segments", "athd_encode_workspace_bytes", "athd_encode", "athd_pack_spectrum",
             "athd_head_output_workspace_bytes", "athd_head_output", "athd_head_output_backward",
             "athd_head_cond_workspace_bytes", "athd_head_cond", "athd_head_cond_backward",
-            "athd_head_dec_workspace_bytes", "athd_head_dec_level", "athd_head_dec_level_backward"]
+            "athd_head_dec_workspace_bytes", "athd_head_dec_level", "athd_head_dec_level_backward",
+            "athd_head_step_workspace_bytes", "athd_head_step"]
 
 F32, BF16 = 0, 1
 
 
 class AthdError(RuntimeError):
     pass
+
+
+def step_table(tensors):
+    """The host table of athd_head_step from (param_ptr, grad_ptr, exp_avg_ptr, exp_avg_sq_ptr, n) tuples"""
+    return (StepTensor * len(tensors))(*[StepTensor(*t) for t in tensors])
+
+
+def head_step_workspace_bytes(table) -> int:
+    """athd_head_step_workspace_bytes of a `step_table`; 0 = a table athd_head_step refuses"""
+    return int(lib.athd_head_step_workspace_bytes(table, len(table)))
+
+
+def head_step(table, hparams: StepHparams, grad_scale_ptr, found_inf_ptr, step_ptr, stats_ptr, ws_ptr, ws_bytes,
+              stream_ptr):
+    """athd_head_step: clip + AdamW over the table's tensors, enqueued on the stream; raises on a refused call"""
+    rc = lib.athd_head_step(table, len(table), _c.byref(hparams), grad_scale_ptr, found_inf_ptr, step_ptr, stats_ptr,
+                            ws_ptr, ws_bytes, stream_ptr)
+    if rc != 0:
+        raise AthdError(f"athd_head_step failed ({rc})")
 
 
 def required_keys():

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/athd.h"
 #include "gemm.h"
 
 namespace athd {
@@ -349,5 +350,16 @@ int head_dec_bwd_launch(int level, const float* gy, const float* x, const float*
                         const float* gamma, const float* beta, const float* stats, int64_t B, int64_t M, int64_t inner,
                         int64_t Lt, float* gx, float* gw, float* gb, float* ggamma, float* gbeta, float* ws,
                         hipStream_t s);
+
+// head_step.hip: head training's update step (include/athd.h `athd_head_step`: global gradient norm, clip, AdamW), all
+// f32 storage, fp64 arithmetic.  A tensor is cut into chunks of HEAD_STEP_CHUNK elements, one workgroup each;
+// head_step_chunks() is their number (0 = n_tensors outside 1..64, an n < 1 or more than HEAD_STEP_MAX_CHUNKS) and the
+// number of doubles `part` holds.  t and hp are host data, copied into the kernel arguments.  Returns 0, -1 for a bad
+// argument (nothing launched), or the positive hipError_t of a failed launch.  Every update workgroup adds all partials
+// itself, so the work grows with the square of the chunk count: the limit keeps that sum at a few microseconds.
+constexpr int64_t HEAD_STEP_CHUNK = 4096, HEAD_STEP_MAX_CHUNKS = 4096;
+int64_t head_step_chunks(const athd_step_tensor* t, int n_tensors);
+int head_step_launch(const athd_step_tensor* t, int n_tensors, const athd_step_hparams& hp, const float* grad_scale,
+                     const float* found_inf, int32_t* step, float* stats, double* part, hipStream_t s);
 
 }  // namespace athd

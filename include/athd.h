@@ -364,6 +364,50 @@ int athd_gather_train_segments(const float* stems, int n_src, int64_t length, co
                                const double* gain, const uint8_t* swap, int64_t rows, int64_t seg_samples, float* out,
                                void* stream);
 
+/* ---- Training update step: clip_grad_norm_ + torch.optim.AdamW.step of train_epoch (src/train.py:80-95) in one call,
+ * with the AMP scaler's unscale and skip ----
+ * Stream-only like the training ends: no context, no allocation, no host synchronisation, capturable in a graph.
+ *
+ * t: a HOST table of n_tensors (1..ATHD_STEP_MAX_TENSORS) entries; param, grad, exp_avg, exp_avg_sq are device f32
+ * arrays of n >= 1 elements each, 4-byte aligned (16-byte accesses are used for a tensor whose four pointers are
+ * 16-byte aligned).  The table is copied into the kernel arguments at the call: nothing has to stay alive, and the
+ * pointers may differ from call to call.  hp: host.  The hyper-parameters are doubles: a float beta2 = 0.999f would
+ * put a relative 1.3e-5 into (1 - beta2), a hundred times the rounding of a float32 step.
+ *
+ *   total = sum over every element of every tensor of grad^2       fp64, fixed order: one partial per chunk of 4096
+ *                                                                  elements into `workspace`, added in index order
+ *   inv   = grad_scale ? 1 / *grad_scale : 1                       (torch.amp.GradScaler's optimizer.grad_scale)
+ *   norm  = sqrt(total) * inv
+ *   coef  = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1    clip_grad_norm_'s always-applied clamped coefficient
+ *   skipped = (found_inf && *found_inf != 0) || !isfinite(norm)
+ * If skipped, no parameter and no moment is written and *step stays.  Otherwise t = *step + 1 and per element, evaluated
+ * in fp64 and rounded once per stored value, with g = grad * inv * coef, in torch.optim.AdamW's order:
+ *   p *= 1 - lr * weight_decay;   m = beta1 m + (1 - beta1) g;   v = beta2 v + (1 - beta2) g^2;
+ *   p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps);      *step = t
+ * stats: device, 4 floats out = { norm, coef, skipped (0 or 1), the counter after the call }.
+ *
+ * Two deliberate differences from torch: the gradients are read-only (clip_grad_norm_ rewrites .grad), and a
+ * non-finite norm skips the step and reports it in stats[2], where torch without a scaler multiplies every gradient by
+ * NaN and poisons every parameter.
+ *
+ * Three launches: the partial sums, the update (every workgroup adds the partials itself, in the same order, so all
+ * hold the same total bit for bit), and a one-workgroup tail whose first thread writes stats and the counter; no workgroup reads a word
+ * that another workgroup of the same launch writes, and there are no atomics: the same bits on every run.
+ * workspace: device, 8-byte aligned, athd_head_step_workspace_bytes() bytes, not initialised by the caller.  At most
+ * 4096 chunks (2^24 elements when every tensor fills its chunks; the head has 763): every workgroup of the update adds
+ * all partials, so that sum grows with the square of the chunk count and the limit keeps it at a few microseconds.
+ * n_tensors outside 1..64, an n < 1, more chunks than
+ * that (athd_head_step_workspace_bytes returns 0 for these), a null or misaligned pointer: ATHD_EINVAL; a short
+ * workspace: ATHD_EWORKSPACE; nothing is launched. */
+typedef struct { float* param; const float* grad; float* exp_avg; float* exp_avg_sq; int64_t n; } athd_step_tensor;
+typedef struct { double lr, beta1, beta2, eps, weight_decay, max_norm; } athd_step_hparams;  /* max_norm <= 0: no clipping */
+#define ATHD_STEP_MAX_TENSORS 64
+size_t athd_head_step_workspace_bytes(const athd_step_tensor* t /*host*/, int n_tensors);
+int athd_head_step(const athd_step_tensor* t /*host*/, int n_tensors, const athd_step_hparams* hp /*host*/,
+                   const float* grad_scale /*device, or NULL*/, const float* found_inf /*device, or NULL*/,
+                   int32_t* step /*device, in/out*/, float* stats /*device, 4 floats out*/,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Audio front end: the user path of app.py:74-126 (a file of any rate, mono or stereo) ----
  * Stream-only like the track level: no context, no host synchronisation, no device allocation, work enqueued on
  * `stream`.
