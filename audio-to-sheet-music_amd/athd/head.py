@@ -6,8 +6,11 @@ the HTDemucs encoders, the cross-transformer and CLAP run frozen under `no_grad`
 differentiable by autograd on any device and dtype; `HeadTrainer` joins the two behind the `model(mixture, prompts)`
 call that `athd.train.train_epoch` expects.  The model's backward stays torch's, except for the output
 stage (mask, iSTFT, denormalisation), which `native_output=True` runs natively in both directions (`NativeOutputStage`),
-the text-conditioning stage, which `native_cond=True` does (`NativeCondStage`), and the two decoders, which
-`native_decoders=True` does level by level (`NativeDecoderLevel`).
+the text-conditioning stage, which `native_cond=True` does (`NativeCondStage`), the two decoders, which
+`native_decoders=True` does level by level (`NativeDecoderLevel`), and what is left between them, which
+`native_proj=True` does: the attention vector (`NativeAttnVector`) and `freq_out` / `time_out`, fused with the output
+stage into one node (`NativeProjOutput`).  With all four options on, every forward and backward kernel of the head is the
+library's; torch allocates the tensors and runs the Function plumbing.
 
 `TrainableHead.state_dict()` has exactly the 50 reference key names and shapes outside `htdemucs.` / `clap.`
 (`athd.weights.hot_path_spec`), so a trained head drops into a reference-format checkpoint and loads straight back into
@@ -76,11 +79,18 @@ class _TextAttention(nn.Module):
         return [self.q_proj.weight, self.q_proj.bias, self.k_proj.weight, self.k_proj.bias, self.norm_q.weight,
                 self.norm_q.bias]
 
-    def forward_native(self, x: torch.Tensor, xt: torch.Tensor, text_emb: torch.Tensor, nctx):
-        """`forward` through `NativeCondStage`: x, xt contiguous float32 channel-first; float32 whatever autocast says"""
+    def forward_native(self, x: torch.Tensor, xt: torch.Tensor, text_emb: torch.Tensor, nctx, native_vec: bool = False):
+        """`forward` through `NativeCondStage`: x, xt contiguous float32 channel-first; float32 whatever autocast says.
+        `native_vec`: the attention vector by `NativeAttnVector` instead of `attn_vector`'s three `F.linear`."""
         with torch.autocast(device_type=x.device.type, enabled=False):
-            a = _DeadParams.apply(self.attn_vector(text_emb.reshape(text_emb.shape[0], -1).float()),
-                                  *self.dead_parameters())
+            text = text_emb.reshape(text_emb.shape[0], -1).float()
+            if native_vec:
+                a = NativeAttnVector.apply(text, self.v_proj.weight, self.v_proj.bias, self.attn.in_proj_weight,
+                                           self.attn.in_proj_bias, self.attn.out_proj.weight, self.attn.out_proj.bias,
+                                           nctx)
+            else:
+                a = self.attn_vector(text)
+            a = _DeadParams.apply(a, *self.dead_parameters())
             w = (self.out_mlp[0].weight, self.out_mlp[0].bias, self.out_mlp[2].weight, self.out_mlp[2].bias,
                  self.norm_out.weight, self.norm_out.bias)
             return NativeCondStage.apply(x, a, *w, nctx), NativeCondStage.apply(xt, a, *w, nctx)
@@ -201,6 +211,90 @@ class _DeadParams(torch.autograd.Function):
         return (g,) + tuple(torch.zeros_like(p) for p in ctx.saved_tensors)
 
 
+class NativeAttnVector(torch.autograd.Function):
+    """`_TextAttention.attn_vector` in libathd.so, both directions (`athd_head_attn_vec`, `athd_head_attn_vec_backward`,
+    include/athd.h): `text (B, 512)` and the raw `v_proj`, `attn.in_proj_*` (whole) and `attn.out_proj` parameters ->
+    `a (B, 384)`.  The backward writes whole-tensor gradients, the query and key thirds of `in_proj_*` as exact zeros (no
+    slicing autograd); `text` gets no gradient.  Saved: `text` and the two (B, 384) intermediates."""
+
+    @staticmethod
+    def forward(ctx, text, wv, bv, w_in, b_in, wo, bo, nctx):
+        B = text.shape[0]
+        params = (wv, bv, w_in, b_in, wo, bo)
+        t = [p.detach().float().contiguous() for p in (text,) + params]
+        a = torch.empty((B, MODEL_DIM), dtype=torch.float32, device=text.device)
+        keep = torch.empty((B, 2, MODEL_DIM), dtype=torch.float32, device=text.device)
+        nctx.head_attn_vec(*[p.data_ptr() for p in t], B, a.data_ptr(), keep.data_ptr(),
+                           torch.cuda.current_stream(text.device).cuda_stream)
+        ctx.save_for_backward(t[0], keep, t[3], t[5])
+        ctx.nctx, ctx.dtypes = nctx, [p.dtype for p in params]
+        return a
+
+    @staticmethod
+    def backward(ctx, g):
+        text, keep, w_in, wo = ctx.saved_tensors
+        g = g.float().contiguous()
+        D = MODEL_DIM
+        shapes = ((D, text.shape[1]), (D,), (3 * D, D), (3 * D,), (D, D), (D,))
+        grads = [torch.empty(sh, dtype=torch.float32, device=g.device) for sh in shapes]
+        ctx.nctx.head_attn_vec_backward(g.data_ptr(), text.data_ptr(), keep.data_ptr(), w_in.data_ptr(), wo.data_ptr(),
+                                        text.shape[0], *[t.data_ptr() for t in grads],
+                                        torch.cuda.current_stream(g.device).cuda_stream)
+        return (None,) + tuple(t.to(d) for t, d in zip(grads, ctx.dtypes)) + (None,)
+
+
+class NativeProjOutput(torch.autograd.Function):
+    """`freq_out`, `time_out` and the output stage as one node in libathd.so: `(xd (B, 4, Ts, Ts), xtd (B, 4, T))`, the
+    decoders' channel-first outputs, -> `(B, 2, T)`.  Forward: `athd_head_proj` twice, straight into the layouts
+    `athd_head_output` reads, then `athd_head_output`.  Backward: `athd_head_output_backward`, then
+    `athd_head_proj_backward` on its `grad_logits` and on the incoming gradient itself (channel-first, scaled per item by
+    `stdt` inside the kernel).  No permute, no copy and no elementwise torch op in between.  `spec`, `meant` and `stdt`
+    get no gradient (they come from the frozen half).  Saved: the two inputs, the logits, `spec`, `stdt`, the two weights."""
+
+    @staticmethod
+    def forward(ctx, xd, xtd, wf, bf, wt, bt, spec, meant, stdt, nctx):
+        B, _, R, S = xd.shape
+        T = xtd.shape[2]
+        dev = xd.device
+        params = (wf, bf, wt, bt)
+        wf_, bf_, wt_, bt_ = [p.detach().float().contiguous() for p in params]
+        std = stdt.detach().reshape(B).float().contiguous()
+        tnorm = torch.stack((meant.detach().reshape(B).float(), std), dim=1).contiguous()
+        logits = torch.empty((B, S, R, 2), dtype=torch.float32, device=dev)
+        xt = torch.empty((B, T, 2), dtype=torch.float32, device=dev)
+        out = torch.empty((B, 2, T), dtype=torch.float32, device=dev)
+        ws = torch.empty(max(nctx.head_output_workspace_bytes(B, T), 16), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nctx.head_proj(xd.data_ptr(), wf_.data_ptr(), bf_.data_ptr(), B, R, S, logits.data_ptr(), stream)
+        nctx.head_proj(xtd.data_ptr(), wt_.data_ptr(), bt_.data_ptr(), B, 1, T, xt.data_ptr(), stream)
+        nctx.head_output(logits.data_ptr(), spec.data_ptr(), xt.data_ptr(), tnorm.data_ptr(), B, T, out.data_ptr(),
+                         ws.data_ptr(), ws.numel(), stream)
+        ctx.save_for_backward(xd, xtd, wf_, wt_, logits, spec, std)
+        ctx.nctx, ctx.dtypes = nctx, [p.dtype for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xd, xtd, wf, wt, logits, spec, std = ctx.saved_tensors
+        B, _, R, S = xd.shape
+        T = xtd.shape[2]
+        nctx, dev = ctx.nctx, g.device
+        g = g.float().contiguous()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        grad_logits, gxd, gxtd = torch.empty_like(logits), torch.empty_like(xd), torch.empty_like(xtd)
+        gwf, gbf, gwt, gbt = new(*wf.shape), new(2), new(*wt.shape), new(2)
+        nws = max(nctx.head_proj_workspace_bytes(B, R, S), nctx.head_proj_workspace_bytes(B, 1, T), 16)
+        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        nctx.head_output_backward(g.data_ptr(), logits.data_ptr(), spec.data_ptr(), B, T, grad_logits.data_ptr(), stream)
+        nctx.head_proj_backward(grad_logits.data_ptr(), 0, None, xd.data_ptr(), wf.data_ptr(), B, R, S, gxd.data_ptr(),
+                                gwf.data_ptr(), gbf.data_ptr(), ws.data_ptr(), nws, stream)
+        # (the same stream orders the two calls, so they share the workspace)
+        nctx.head_proj_backward(g.data_ptr(), 1, std.data_ptr(), xtd.data_ptr(), wt.data_ptr(), B, 1, T, gxtd.data_ptr(),
+                                gwt.data_ptr(), gbt.data_ptr(), ws.data_ptr(), nws, stream)
+        return (gxd, gxtd) + tuple(t.to(d) for t, d in zip((gwf, gbf, gwt, gbt), ctx.dtypes)) + (None, None, None, None)
+
+
 class NativeCondStage(torch.autograd.Function):
     """The text-conditioning stage after the attention vector, in libathd.so, both directions (`athd_head_cond`,
     `athd_head_cond_backward`, include/athd.h): `x (B, 384, ...)` channel-first float32 as `athd_encode` exports it,
@@ -289,9 +383,18 @@ class TrainableHead(nn.Module):
     `native_decoders=True` does the same for both decoders (`NativeDecoderLevel`, four levels each, on the conditioned
     features' channel-first layout as it is; `freq_out` / `time_out` stay torch's).  Same requirements and refusals as
     `native_cond` (bound model, float32 parameters on its GPU, float32 features and skips on that GPU); float32 under
-    autocast.  The three options are independent and compose."""
+    autocast.  The three options are independent and compose; with all three on torch's autograd is left with
+    `freq_out` / `time_out` and the attention vector, unless `native_proj` is on as well.
 
-    def __init__(self, native_output: bool = False, native_cond: bool = False, native_decoders: bool = False):
+    `native_proj=True` does the same for what is left: the attention vector (`NativeAttnVector`) and `freq_out` /
+    `time_out`, which become one node with the output stage (`NativeProjOutput`).  Its inputs and outputs exist only in
+    those stages' layouts, so it needs `native_output` and `native_cond` to be on, and what they need; it raises
+    otherwise, and when a decoder emits another length than the segment's (the torch resize is not kept inside).  It is
+    independent of `native_decoders` (torch's channel-first decoder output is taken after `.float().contiguous()`);
+    float32 under autocast.  With it the six wholly dead tensors keep their exact-zero gradients (`_DeadParams`)."""
+
+    def __init__(self, native_output: bool = False, native_cond: bool = False, native_decoders: bool = False,
+                 native_proj: bool = False):
         super().__init__()
         self.text_attn = _TextAttention()
         self.freq_decoder = _Decoder(True)
@@ -301,6 +404,7 @@ class TrainableHead(nn.Module):
         self.native_output = bool(native_output)
         self.native_cond = bool(native_cond)
         self.native_decoders = bool(native_decoders)
+        self.native_proj = bool(native_proj)
         object.__setattr__(self, "_native_model", None)      # a plain attribute, not a submodule
         object.__setattr__(self, "_spec_cache", None)        # (weakref to z, its version, packed spectrum)
 
@@ -324,22 +428,54 @@ class TrainableHead(nn.Module):
         object.__setattr__(self, "_spec_cache", (weakref.ref(z), z._version, spec))
         return spec
 
-    def _native_stage(self, f: EncodedFeatures, xd: torch.Tensor, xtd: torch.Tensor) -> torch.Tensor:
+    def _check_native_output(self, f: EncodedFeatures, opt: str = "native_output=True"):
         model, p = self._native_model, self.freq_out.weight
         if model is None:
-            raise RuntimeError("native_output=True needs the native model: call head.bind(model) (HeadTrainer does)")
+            raise RuntimeError(f"{opt} needs the native model: call head.bind(model) (HeadTrainer does)")
         if p.dtype != torch.float32 or p.device.type != "cuda" or p.device != model.device:
-            raise RuntimeError(f"native_output=True needs float32 parameters on the model's device {model.device}, got "
+            raise RuntimeError(f"{opt} needs float32 parameters on the model's device {model.device}, got "
                                f"{p.dtype} on {p.device}; leave the option off for the torch output stage")
         z = f.z
         if z.dtype != torch.complex64 or z.device != p.device or z.shape[1:3] != (2, 2048):
-            raise RuntimeError("native_output=True needs the features' z as complex64 (B, 2, 2048, Ts) on the model's "
+            raise RuntimeError(f"{opt} needs the features' z as complex64 (B, 2, 2048, Ts) on the model's "
                                "device")
         if z.shape[3] > 2048 or z.shape[3] != -(-f.length // HOP):
-            raise RuntimeError(f"native_output=True covers segments of at most 2048 frames, got {z.shape[3]} frames "
+            raise RuntimeError(f"{opt} covers segments of at most 2048 frames, got {z.shape[3]} frames "
                                f"for {f.length} samples")
-        return NativeOutputStage.apply(xd, xtd, self.packed_spectrum(z), self._cast(f.meant), self._cast(f.stdt),
+
+    def _native_stage(self, f: EncodedFeatures, xd: torch.Tensor, xtd: torch.Tensor) -> torch.Tensor:
+        model = self._native_model
+        self._check_native_output(f)
+        return NativeOutputStage.apply(xd, xtd, self.packed_spectrum(f.z), self._cast(f.meant), self._cast(f.stdt),
                                        model._ensure_ctx())
+
+    def _check_native_proj(self):
+        model, p = self._native_model, self.time_out.weight
+        if not (self.native_output and self.native_cond):
+            raise RuntimeError("native_proj=True needs native_output=True and native_cond=True: its inputs and outputs "
+                               "exist only in those stages' layouts")
+        if model is None:
+            raise RuntimeError("native_proj=True needs the native model: call head.bind(model) (HeadTrainer does)")
+        if p.dtype != torch.float32 or p.device.type != "cuda" or p.device != model.device:
+            raise RuntimeError(f"native_proj=True needs float32 parameters on the model's device {model.device}, got "
+                               f"{p.dtype} on {p.device}; leave the option off for the torch projections")
+
+    def _native_proj_stage(self, f: EncodedFeatures, xd: torch.Tensor, xtd: torch.Tensor) -> torch.Tensor:
+        """`freq_out`, `time_out` and the output stage on the decoders' outputs xd (B, 4, Ts, Ts), xtd (B, 4, T)"""
+        p = self.freq_out.weight
+        self._check_native_output(f, "native_proj=True")
+        B, Ts, T = f.z.shape[0], f.z.shape[3], f.length
+        if tuple(xd.shape) != (B, DEC_CH[-1], Ts, Ts):
+            raise RuntimeError(f"native_proj=True needs the frequency decoder's output as (B, {DEC_CH[-1]}, {Ts}, {Ts}), "
+                               f"got {tuple(xd.shape)}")
+        if tuple(xtd.shape) != (B, DEC_CH[-1], T):
+            raise RuntimeError(f"native_proj=True needs the time decoder to emit the segment's length {T}, got "
+                               f"{tuple(xtd.shape)}: the resize in front of the output stage is not part of it")
+        with torch.autocast(device_type=p.device.type, enabled=False):
+            return NativeProjOutput.apply(xd.float().contiguous(), xtd.float().contiguous(), self.freq_out.weight,
+                                          self.freq_out.bias, self.time_out.weight, self.time_out.bias,
+                                          self.packed_spectrum(f.z), self._cast(f.meant), self._cast(f.stdt),
+                                          self._native_model._ensure_ctx())
 
     def _native_cond_stage(self, f: EncodedFeatures, text_emb: torch.Tensor):
         model, p = self._native_model, self.text_attn.norm_out.weight
@@ -353,7 +489,8 @@ class TrainableHead(nn.Module):
                     or t.shape[1] != MODEL_DIM or t.numel() == 0):
                 raise RuntimeError(f"native_cond=True needs the features' {name} as contiguous float32 (B, {MODEL_DIM}, "
                                    f"...) on the model's device, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        return self.text_attn.forward_native(f.x_enc, f.xt_enc, text_emb.to(p.device), model._ensure_ctx())
+        return self.text_attn.forward_native(f.x_enc, f.xt_enc, text_emb.to(p.device), model._ensure_ctx(),
+                                             native_vec=self.native_proj)
 
     def _native_decoder_stage(self, f: EncodedFeatures, x_cond: torch.Tensor, xt_cond: torch.Tensor):
         model, p = self._native_model, self.freq_decoder.layers[0][0].weight
@@ -398,9 +535,11 @@ class TrainableHead(nn.Module):
         p = self.freq_out.weight
         return t.to(device=p.device, dtype=p.dtype)
 
-    def branches(self, f: EncodedFeatures, text_emb: torch.Tensor):
-        """(x_cond, xt_cond, freq_out(freq_decoder(..)), time_out(time_decoder(..))): everything before the mask"""
+    def decoded(self, f: EncodedFeatures, text_emb: torch.Tensor):
+        """(x_cond, xt_cond, freq_decoder(..), time_decoder(..)): everything before `freq_out` / `time_out`"""
         cast = self._cast
+        if self.native_proj:
+            self._check_native_proj()
         if self.native_cond:
             x_cond, xt_cond = self._native_cond_stage(f, text_emb)
         else:
@@ -412,11 +551,20 @@ class TrainableHead(nn.Module):
         else:
             xd = self.freq_decoder(x_cond, [cast(s) for s in f.skips[::-1]], list(f.lengths[::-1]))
             xtd = self.time_decoder(xt_cond, [cast(s) for s in f.skips_t[::-1]], list(f.lengths_t[::-1]))
+        return x_cond, xt_cond, xd, xtd
+
+    def branches(self, f: EncodedFeatures, text_emb: torch.Tensor):
+        """(x_cond, xt_cond, freq_out(freq_decoder(..)), time_out(time_decoder(..))): everything before the mask, the
+        two projections as torch's channel-first convolutions whatever `native_proj` says"""
+        x_cond, xt_cond, xd, xtd = self.decoded(f, text_emb)
         return x_cond, xt_cond, self.freq_out(xd), self.time_out(xtd)
 
     def forward(self, f: EncodedFeatures, text_emb: torch.Tensor) -> torch.Tensor:
         p = self.freq_out.weight
         cast = self._cast
+        if self.native_proj:
+            _, _, xd, xtd = self.decoded(f, text_emb)
+            return self._native_proj_stage(f, xd, xtd)
         _, _, xd, xtd = self.branches(f, text_emb)
         if self.native_output:
             # (the time branch's resize, when the head emits another length, stays torch's, in front of the Function)
@@ -441,20 +589,21 @@ class HeadTrainer(nn.Module):
     model is a plain attribute (not a submodule): `parameters()`, `train()` and `eval()` are the head's."""
 
     def __init__(self, model, head: Optional[TrainableHead] = None, native_output: bool = False,
-                 native_cond: bool = False, native_decoders: bool = False):
+                 native_cond: bool = False, native_decoders: bool = False, native_proj: bool = False):
         super().__init__()
         object.__setattr__(self, "model", model)
         if head is None:
             if model.device is None:
                 model.to("cuda")
             head = TrainableHead.from_model(model).to(model.device)
-        # native_output / native_cond / native_decoders: the head's last / first / middle stage and its gradient in
-        # libathd.so (TrainableHead); a head that was built with an option keeps it.  Only such a head holds a reference
-        # to the native model.
+        # native_output / native_cond / native_decoders / native_proj: the head's last / first / middle stage and the
+        # projections between them, with their gradients, in libathd.so (TrainableHead); a head that was built with an
+        # option keeps it.  Only such a head holds a reference to the native model.
         head.native_output = bool(native_output or head.native_output)
         head.native_cond = bool(native_cond or head.native_cond)
         head.native_decoders = bool(native_decoders or head.native_decoders)
-        if head.native_output or head.native_cond or head.native_decoders:
+        head.native_proj = bool(native_proj or head.native_proj)
+        if head.native_output or head.native_cond or head.native_decoders or head.native_proj:
             head.bind(model)
         self.head = head
 

@@ -71,6 +71,17 @@ lib.athd_head_dec_level.restype = _c.c_int
 lib.athd_head_dec_level_backward.argtypes = [_c.c_void_p, _c.c_int] + [_c.c_void_p] * 7 + [_c.c_int64] * 4 + [
     _c.c_void_p] * 5 + [_c.c_void_p, _c.c_size_t, _c.c_void_p]
 lib.athd_head_dec_level_backward.restype = _c.c_int
+lib.athd_head_proj_workspace_bytes.argtypes = [_c.c_int64] * 3
+lib.athd_head_proj_workspace_bytes.restype = _c.c_size_t
+lib.athd_head_proj.argtypes = [_c.c_void_p] * 4 + [_c.c_int64] * 3 + [_c.c_void_p, _c.c_void_p]
+lib.athd_head_proj.restype = _c.c_int
+lib.athd_head_proj_backward.argtypes = [_c.c_void_p, _c.c_void_p, _c.c_int] + [_c.c_void_p] * 3 + [_c.c_int64] * 3 + [
+    _c.c_void_p] * 3 + [_c.c_void_p, _c.c_size_t, _c.c_void_p]
+lib.athd_head_proj_backward.restype = _c.c_int
+lib.athd_head_attn_vec.argtypes = [_c.c_void_p] * 8 + [_c.c_int64] + [_c.c_void_p] * 3
+lib.athd_head_attn_vec.restype = _c.c_int
+lib.athd_head_attn_vec_backward.argtypes = [_c.c_void_p] * 6 + [_c.c_int64] + [_c.c_void_p] * 7
+lib.athd_head_attn_vec_backward.restype = _c.c_int
 class StepTensor(_c.Structure):
     """athd_step_tensor (include/athd.h): one tensor of athd_head_step's host table"""
     _fields_ = [("param", _c.c_void_p), ("grad", _c.c_void_p), ("exp_avg", _c.c_void_p), ("exp_avg_sq", _c.c_void_p),
@@ -190,7 +201,9 @@ EXPORTED = ["athd_version", "athd_create", "athd_set_weight", "athd_num_required
             "athd_head_output_workspace_bytes", "athd_head_output", "athd_head_output_backward",
             "athd_head_cond_workspace_bytes", "athd_head_cond", "athd_head_cond_backward",
             "athd_head_dec_workspace_bytes", "athd_head_dec_level", "athd_head_dec_level_backward",
-            "athd_head_step_workspace_bytes", "athd_head_step"]
+            "athd_head_step_workspace_bytes", "athd_head_step",
+            "athd_head_proj_workspace_bytes", "athd_head_proj", "athd_head_proj_backward",
+            "athd_head_attn_vec", "athd_head_attn_vec_backward"]
 
 F32, BF16 = 0, 1
 
@@ -318,6 +331,29 @@ class Context:
                                                      beta_ptr, stats_ptr, B, M, inner, Lt, grad_x_ptr, grad_w_ptr,
                                                      grad_bias_ptr, grad_gamma_ptr, grad_beta_ptr, ws_ptr, ws_bytes,
                                                      stream_ptr), "athd_head_dec_level_backward")
+
+    @staticmethod
+    def head_proj_workspace_bytes(B: int, R: int, S: int) -> int:
+        return int(lib.athd_head_proj_workspace_bytes(B, R, S))
+
+    def head_proj(self, x_ptr, w_ptr, bias_ptr, B, R, S, y_ptr, stream_ptr):
+        self._check(lib.athd_head_proj(self.h, x_ptr, w_ptr, bias_ptr, B, R, S, y_ptr, stream_ptr), "athd_head_proj")
+
+    def head_proj_backward(self, grad_y_ptr, grad_channel_first, scale_ptr, x_ptr, w_ptr, B, R, S, grad_x_ptr, grad_w_ptr,
+                           grad_b_ptr, ws_ptr, ws_bytes, stream_ptr):
+        self._check(lib.athd_head_proj_backward(self.h, grad_y_ptr, int(bool(grad_channel_first)), scale_ptr, x_ptr,
+                                                w_ptr, B, R, S, grad_x_ptr, grad_w_ptr, grad_b_ptr, ws_ptr, ws_bytes,
+                                                stream_ptr), "athd_head_proj_backward")
+
+    def head_attn_vec(self, text_ptr, wv_ptr, bv_ptr, w_in_ptr, b_in_ptr, wo_ptr, bo_ptr, B, a_ptr, keep_ptr, stream_ptr):
+        self._check(lib.athd_head_attn_vec(self.h, text_ptr, wv_ptr, bv_ptr, w_in_ptr, b_in_ptr, wo_ptr, bo_ptr, B, a_ptr,
+                                           keep_ptr, stream_ptr), "athd_head_attn_vec")
+
+    def head_attn_vec_backward(self, grad_a_ptr, text_ptr, keep_ptr, w_in_ptr, wo_ptr, B, grad_wv_ptr, grad_bv_ptr,
+                               grad_w_in_ptr, grad_b_in_ptr, grad_wo_ptr, grad_bo_ptr, stream_ptr):
+        self._check(lib.athd_head_attn_vec_backward(self.h, grad_a_ptr, text_ptr, keep_ptr, w_in_ptr, wo_ptr, B,
+                                                    grad_wv_ptr, grad_bv_ptr, grad_w_in_ptr, grad_b_in_ptr, grad_wo_ptr,
+                                                    grad_bo_ptr, stream_ptr), "athd_head_attn_vec_backward")
 
     def profile_start(self, kernel: str | None = None):
         """Time every launch of `kernel` (rocprof symbol short form; None = all kernels) with HIP events."""

@@ -233,15 +233,21 @@ def _resume(c: SimpleNamespace, trainer, optimizer, scheduler) -> int:
 
 
 def train(config: Union[str, Path, dict], *, model=None, tokenizer=None, text_table=None, native: bool = True,
-          dtype: str = "bf16"):
+          dtype: str = "bf16", seed: Optional[int] = None):
     """The training job (`src/train.py:274-605`).  `config`: a YAML path or the loaded dict (CONFIG).  `model`: a loaded
     `AudioTextHTDemucs` to train the head of; without it `training.init_checkpoint` is loaded through `load_model`
-    (`dtype`, `tokenizer=` / `text_table=` as there).  `native=True` trains with the head's three native stages and
-    `HeadAdamW`; `native=False` with the torch stages and `torch.optim.AdamW`.
+    (`dtype`, `tokenizer=` / `text_table=` as there).  `native=True` trains with every native stage of the head (the
+    four `native_*` options) and `HeadAdamW`; `native=False` with the torch stages and `torch.optim.AdamW`.  `seed`
+    seeds Python's `random` (the cut, gain, swap and prompt of every batch) and `torch.manual_seed` (the subsets and
+    the order of the items), as `athd.validate --seed` does; None leaves both generators as they are.
 
-    Returns {"final_train_metrics", "final_val_metrics", "best_sdr"}.  Nothing here asks torch for deterministic
-    algorithms: `athd_head_step` and the native stages repeat bit for bit, torch's own convolution gradients (`time_out`)
-    do not unless `torch.backends.cudnn.deterministic` is set by the caller."""
+    Returns {"final_train_metrics", "final_val_metrics", "best_sdr"}.  With `native=True` every forward and backward
+    kernel of the head and the update step are the library's and repeat bit for bit, so two runs from the same model,
+    data, config and `seed` write the same bits into their checkpoints; nothing here sets a torch switch for that
+    (`torch.backends.cudnn.deterministic` is left alone).  `native=False` leaves the gradients to torch's autograd,
+    whose convolution gradients differ from run to run unless the caller sets that switch."""
+    import random
+
     from .head import HeadTrainer
     from .inference import load_config, load_model
     from .musdb import STEM_PROMPTS, MusDBTracks
@@ -249,6 +255,9 @@ def train(config: Union[str, Path, dict], *, model=None, tokenizer=None, text_ta
     from .train_data import TrainSegmentDataset
     from .validate import SegmentDataset, validate
 
+    if seed is not None:
+        random.seed(int(seed))
+        torch.manual_seed(int(seed))
     c = read_config(config if isinstance(config, dict) else load_config(config))
     if c.use_wandb:
         raise ValueError("wandb.use_wandb is true (the reference's default): wandb logging is not part of athd.train; "
@@ -277,7 +286,7 @@ def train(config: Union[str, Path, dict], *, model=None, tokenizer=None, text_ta
     device = model.device                                   # with its index: where the batches are cut
 
     print("Building AudioTextHTDemucs model...")
-    trainer = HeadTrainer(model, native_output=native, native_cond=native, native_decoders=native)
+    trainer = HeadTrainer(model, native_output=native, native_cond=native, native_decoders=native, native_proj=native)
     # the frozen half has no torch parameters: it is counted over the tensors the native model holds
     trainable = sum(p.numel() for p in trainer.parameters() if p.requires_grad)
     head_names = set(trainer.state_dict())
@@ -334,7 +343,7 @@ def train(config: Union[str, Path, dict], *, model=None, tokenizer=None, text_ta
 
 def main(argv=None) -> int:
     """`python -m athd.train --config config.yaml [--init-checkpoint PATH] [--epochs N] [--no-native] [--dtype
-    f32|bf16]`: `train()` on the config, with the three overrides."""
+    f32|bf16] [--seed K]`: `train()` on the config, with the three overrides."""
     ap = argparse.ArgumentParser(prog="python -m athd.train",
                                  description="Train the head on the frozen native encoder (src/train.py train()).")
     ap.add_argument("--config", default="config.yaml")
@@ -342,6 +351,7 @@ def main(argv=None) -> int:
     ap.add_argument("--epochs", type=int, default=None, help="overrides training.num_epochs")
     ap.add_argument("--no-native", action="store_true", help="torch head stages and torch.optim.AdamW")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="bf16", help="the frozen half's context")
+    ap.add_argument("--seed", type=int, default=None, help="seeds random and torch.manual_seed; with the native stages (no --no-native) a run repeats bit for bit")
     args = ap.parse_args(argv)
 
     from .inference import load_config
@@ -351,7 +361,7 @@ def main(argv=None) -> int:
         training_cfg["init_checkpoint"] = args.init_checkpoint
     if args.epochs is not None:
         training_cfg["num_epochs"] = args.epochs
-    train(cfg, native=not args.no_native, dtype=args.dtype)
+    train(cfg, native=not args.no_native, dtype=args.dtype, seed=args.seed)
     return 0
 
 

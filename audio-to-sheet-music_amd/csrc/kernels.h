@@ -362,4 +362,31 @@ int64_t head_step_chunks(const athd_step_tensor* t, int n_tensors);
 int head_step_launch(const athd_step_tensor* t, int n_tensors, const athd_step_hparams& hp, const float* grad_scale,
                      const float* found_inf, int32_t* step, float* stats, double* part, hipStream_t s);
 
+// head_proj.hip: head training's output projections (include/athd.h `athd_head_proj*`: freq_out / time_out, a 1x1
+// convolution 4 -> 2 channels), all f32.  x, gx [B][4][R][S]; y [B][S][R][2]; gy in y's layout or, channel_first,
+// [B][2][R][S]; w [2][4], bias [2]; scale nullptr or [B].  part: head_proj_ws_doubles(B, R, S) doubles (0 = shape out of
+// range: B in [1, 65535], R in [1, HEAD_PROJ_MAX_R], S in [1, HEAD_PROJ_MAX_S], R S <= HEAD_PROJ_MAX_RS), ten per
+// workgroup of the larger of the backward's two grids.  The big tensors are 16-byte aligned.  Every output element is
+// written; fixed summation order, no atomics.  Each returns -1 for a bad argument (nothing launched) or a HIP error.
+constexpr int64_t HEAD_PROJ_CHUNK = 4096;
+constexpr int64_t HEAD_PROJ_MAX_R = 4096, HEAD_PROJ_MAX_S = 1 << 22, HEAD_PROJ_MAX_RS = 1 << 22;
+int64_t head_proj_ws_doubles(int64_t B, int64_t R, int64_t S);
+int head_proj_fwd_launch(const float* x, const float* w, const float* bias, int64_t B, int64_t R, int64_t S, float* y,
+                         hipStream_t s);
+int head_proj_bwd_launch(const float* gy, int channel_first, const float* scale, const float* x, const float* w,
+                         int64_t B, int64_t R, int64_t S, float* gx, float* gw, float* gb, double* part, hipStream_t s);
+
+// head_proj.hip: the text cross-attention's vector per item (include/athd.h `athd_head_attn_vec*`), all f32 storage,
+// sums in double.  text [B][512]; wv [384][512]; w_in [1152][384] (the value third is read); wo [384][384];
+// a [B][384]; keep [B][2][384] = {v_proj(text), in_proj_v(..)}.  The forward takes B in [1, 65535], the backward B in
+// [1, HEAD_ATTN_MAX_B]: it keeps its two
+// (B, 384) intermediates in the dead two thirds of gw_in until its last launch zeroes them.
+constexpr int HEAD_ATTN_D = 384, HEAD_ATTN_TEXT = 512;
+constexpr int64_t HEAD_ATTN_MAX_B = 384;
+int head_attn_vec_fwd_launch(const float* text, const float* wv, const float* bv, const float* w_in, const float* b_in,
+                             const float* wo, const float* bo, int64_t B, float* a, float* keep, hipStream_t s);
+int head_attn_vec_bwd_launch(const float* ga, const float* text, const float* keep, const float* w_in, const float* wo,
+                             int64_t B, float* gwv, float* gbv, float* gw_in, float* gb_in, float* gwo, float* gbo,
+                             hipStream_t s);
+
 }  // namespace athd

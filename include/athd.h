@@ -247,6 +247,67 @@ int athd_head_dec_level_backward(athd_ctx* ctx, int level, const float* grad_y, 
                                  int64_t M, int64_t inner, int64_t Lt, float* grad_x, float* grad_w, float* grad_bias,
                                  float* grad_gamma, float* grad_beta, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Head training's output projections (freq_out / time_out, ATHTDemucs_v2.py:303-324) in both directions ----
+ * A 1x1 convolution from the last decoder level's 4 channels to 2, from the decoders' channel-first layout straight
+ * into the layouts athd_head_output reads (no permute, no copy in between):
+ *   x (B, 4, R, S) contiguous, w (2, 4) = [out][in] and bias (2) as torch keeps a Conv1d / Conv2d(4, 2, 1) weight,
+ *   y (B, S, R, 2):  y[b][s][r][o] = bias[o] + sum_c w[o][c] x[b][c][r][s]   (f32 fused multiply-adds, c ascending).
+ * Frequency branch: R = rows, S = frames, y is athd_head_output's logits.  Time branch: R = 1, S = T, y is its xt.
+ *
+ * athd_head_proj_backward: grad_y = dL/dy in y's layout (grad_channel_first == 0: what athd_head_output_backward writes)
+ * or as (B, 2, R, S) channel-first (grad_channel_first != 0: the time branch's dL/dout itself), scale NULL or (B)
+ * device floats that multiply item b's gradient first (the time branch's stdt), with the x and w of the forward ->
+ *   g = scale[b] grad_y;  grad_x[b][c][r][s] = sum_o w[o][c] g;  grad_w[o][c] = sum_{b,r,s} g x;  grad_b[o] = sum g.
+ * One pass reads x and grad_y once.  grad_w and grad_b: every workgroup adds its positions in double in a fixed order
+ * and writes ten partial sums to ws; a one-workgroup launch adds the partials in double in index order and rounds once.
+ * No atomics; every output element is written exactly once, none is read: the same bits on every run and under graph
+ * replay.  The arithmetic is f32 (the sums double) in both dtype modes, bit-identical between them; the context is taken
+ * for its device only.
+ *
+ * x, y, grad_y and grad_x must be 16-byte aligned (16-byte accesses are used when R S is a multiple of 4, or R > 1 with
+ * y's layout; 4-byte ones otherwise), the small tensors 4-byte aligned.  ws: device, 16-byte aligned, not initialised by
+ * the caller, athd_head_proj_workspace_bytes(B, R, S) bytes = 80 B max(ceil(R S / 4096), ceil(R / 32) ceil(S / 32) if R > 1).
+ *
+ * Both enqueue on the caller's stream, do not synchronise the host and create no HIP object, so they can be
+ * graph-captured from the first call.  ATHD_ESTATE before athd_finalize; ATHD_EINVAL for a null pointer (scale may be
+ * NULL), B outside [1, 65535], R outside [1, 4096], S outside [1, 4194304], R S > 4194304 (a 2048 x 2048 grid and 47 s
+ * of samples with R = 1 are inside), a misaligned pointer; ATHD_EWORKSPACE for no workspace or one below
+ * athd_head_proj_workspace_bytes (which is 0 for shapes out of range), then ATHD_EINVAL for a misaligned one.  Checked
+ * in that order before anything is read or written. */
+size_t athd_head_proj_workspace_bytes(int64_t B, int64_t R, int64_t S);
+int athd_head_proj(athd_ctx* ctx, const float* x, const float* w, const float* bias, int64_t B, int64_t R, int64_t S,
+                   float* y, void* stream);
+int athd_head_proj_backward(athd_ctx* ctx, const float* grad_y, int grad_channel_first, const float* scale,
+                            const float* x, const float* w, int64_t B, int64_t R, int64_t S, float* grad_x,
+                            float* grad_w, float* grad_b, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- Head training's attention vector (ATHTDemucs_v2.py:21-58 with one key) in both directions ----
+ * a (B, 384) = out_proj(in_proj_v(v_proj(text))), the vector athd_head_cond takes: text (B, 512); wv (384, 512), bv;
+ * w_in (1152, 384) and b_in (1152) the WHOLE in_proj_weight / in_proj_bias, of which the value third (rows 768..1151)
+ * is read; wo (384, 384), bo.  keep (B, 2, 384) = {v_proj(text), in_proj_v(v_proj(text))} per item, what the backward
+ * needs beside text.
+ *
+ * athd_head_attn_vec_backward: grad_a (B, 384) -> grad_wv, grad_bv, grad_wo, grad_bo and the whole grad_w_in
+ * (1152, 384) and grad_b_in (1152), whose query and key thirds are exact zeros.  text gets no gradient.
+ *
+ * Every output element belongs to one wave (forward) or one thread (backward) that sums in double in ascending order
+ * of the inner index, respectively of b, and rounds once; the two gradients that travel between the layers are rounded
+ * to f32 like keep.  No atomics: the same bits on every run and under graph replay, and in both dtype modes.  The
+ * backward keeps its two (B, 384) intermediates in the dead two thirds of grad_w_in until its last launch writes the
+ * zeros, so grad_w_in is scratch while the backward runs and the backward's B is at most 384; the forward takes B up
+ * to 65535.
+ *
+ * Both enqueue on the caller's stream, do not synchronise the host and create no HIP object.  ATHD_ESTATE before
+ * athd_finalize; ATHD_EINVAL for a null pointer, B outside [1, 65535] (forward) or [1, 384] (backward), a pointer that is not 4-byte
+ * aligned.  Checked in
+ * that order before anything is read or written. */
+int athd_head_attn_vec(athd_ctx* ctx, const float* text, const float* wv, const float* bv, const float* w_in,
+                       const float* b_in, const float* wo, const float* bo, int64_t B, float* a, float* keep,
+                       void* stream);
+int athd_head_attn_vec_backward(athd_ctx* ctx, const float* grad_a, const float* text, const float* keep,
+                                const float* w_in, const float* wo, int64_t B, float* grad_wv, float* grad_bv,
+                                float* grad_w_in, float* grad_b_in, float* grad_wo, float* grad_bo, void* stream);
+
 /* ---- Track level: the window loop of test_inference.py:92-141 and sdr_loss (src/loss.py:9-30) ----
  * Windows: start_k = k*hop with hop = chunk_len - overlap, for k = 0 .. athd_num_windows()-1 (while start < length),
  * end_k = min(start_k + chunk_len, length).  Window k is faded by torchaudio Fade(fade_in = k ? overlap : 0,
